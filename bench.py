@@ -16,13 +16,16 @@ only the assignment table and the result sizes travel (RCCL, metadata only).
 Rank 0 prints ONE JSON line:  value = uncompressed MB/s in, whole job.
   roofline      the dominant kernel (LZ77 parse): algorithmic bytes (input read once +
                 stream written once) / its mean duration measured with HIP
-                events on the launch stream, against the 8 TB/s HBM peak.
+                events on the launch stream (in the timed steps), against the 8 TB/s HBM peak.
+A plain run does only that: set up, warm up, time --steps steps, print the line.
+--dump-outputs DIR also writes what the last timed step computed (see dump_outputs).
+--full adds everything else, as separate work after the headline:
   cpu_baseline  the same workload on the host cores: the compiled reference when
                 oracle/_ref/libzsc_ref.so travelled with the repo ("reference"),
                 otherwise the byte-identical oracle ("port"); bounded sample.
   checked       every distinct buffer of the timed batch against the oracle, and every
                 replica against its first copy on the device.
-With one GPU the line also carries the rest of BASELINE's metric (untimed by the headline):
+With one GPU and --full the line also carries the rest of BASELINE's metric (untimed by the headline):
   inflate       BASELINE config 4: gzip members of 4-64 KiB (made by this library's own
                 deflate, checked against the oracle) replicated to --inflate-streams, MB/s
                 out with its own roofline (k_inflate) and CPU baseline.
@@ -41,6 +44,53 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+
+DUMP_SEED = 20251015           # the fixed samples written by --dump-outputs
+DUMP_BYTES = 64_000_000        # everything it writes, .npy headers included
+DUMP_STREAM_BYTES = 14 << 20   # cap of the stream sample, in stream bytes by capacity (4 B each as float32)
+DUMP_LISTED = 1 << 20          # buffers whose length and status are written; beyond, a seeded sample of them
+
+
+def dump_outputs(path: str, d_out, plan, lens, stats) -> dict:
+    """What a caller of the timed path receives after its last step, as .npy files under `path`:
+      stream_lengths.npy  float64 [m]    compressed length of each listed buffer's stream
+      status.npy          float64 [m]    its ZlibReturn
+      listed_index.npy    float64 [m]    which buffers those are -- only written when there are more
+                                         than DUMP_LISTED buffers (otherwise all of them, in order)
+      sample_index.npy    float64 [k]    a fixed, seeded sample of buffers (chosen by the plan's output
+                                         capacities and what is left of the budget, not by what was computed)
+      sample_streams.npy  float32 [sum]  the stream bytes of those buffers, back to back
+    At most DUMP_BYTES in all, whatever the workload."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n = len(lens)
+    rng = np.random.default_rng(DUMP_SEED)
+    listed = None if n <= DUMP_LISTED else np.sort(rng.permutation(n)[:DUMP_LISTED])
+    m = n if listed is None else DUMP_LISTED
+    budget = DUMP_BYTES - 5 * 128 - (16 if listed is None else 24) * m   # (an .npy header is 128 B)
+    order = np.random.default_rng(DUMP_SEED + 1).permutation(n)
+    picks, stream_budget = [], DUMP_STREAM_BYTES
+    for i in order.tolist():
+        cost = 4 * plan.out_caps[i] + 8   # its bytes as float32, and its index
+        if plan.out_caps[i] <= stream_budget and cost <= budget:
+            picks.append(i)
+            stream_budget -= plan.out_caps[i]
+            budget -= cost
+    picks.sort()
+    parts = [d_out[plan.out_offsets[i]:plan.out_offsets[i] + lens[i]] for i in picks]
+    sample = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, dtype=np.uint8)
+    lens_a, stats_a = np.asarray(lens, dtype=np.float64), np.asarray(stats, dtype=np.float64)
+    if listed is not None:
+        lens_a, stats_a = lens_a[listed], stats_a[listed]
+        np.save(os.path.join(path, "listed_index.npy"), listed.astype(np.float64))
+    np.save(os.path.join(path, "stream_lengths.npy"), lens_a)
+    np.save(os.path.join(path, "status.npy"), stats_a)
+    np.save(os.path.join(path, "sample_index.npy"), np.asarray(picks, dtype=np.float64))
+    np.save(os.path.join(path, "sample_streams.npy"), sample.astype(np.float32))
+    return {"dir": path, "buffers": n, "listed_buffers": m, "sampled_buffers": len(picks),
+            "sampled_stream_bytes": int(sample.size)}
 
 
 def cpu_baseline(level: int, seconds_budget: float = 20.0):
@@ -423,6 +473,7 @@ def run_config5(args, rank, world, local, dev):
     olens, stats = plan.results()
     if any(x != 0 for x in stats):
         raise SystemExit(f"rank {rank}: {sum(1 for x in stats if x)} buffers failed")
+    dumped = dump_outputs(args.dump_outputs, d_out, plan, olens, stats) if args.dump_outputs and rank == 0 else None
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -467,6 +518,8 @@ def run_config5(args, rank, world, local, dev):
                                    "input_bytes": count * stride_in, "output_bytes": count * stride_out},
                 "compressed_bytes_total": int(szt[0]), "all_ok": bool(int(okt[0]) == 1),
                 "device": zsc_amd.device_info()}
+        if dumped:
+            line["outputs"] = dumped
         print(json.dumps(line), flush=True)
     plan.close()
     del gathered
@@ -484,11 +537,11 @@ def main() -> None:
     ap.add_argument("--seeds", type=int, default=64,
                     help="distinct seeds among the copies (64 x 11 = 704 distinct buffers, each replicated copies / 64 times)")
     ap.add_argument("--level", type=int, default=6)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--verify", type=int, default=-1,
-                    help="distinct buffers per rank checked against the oracle (-1: all of them)")
+                    help="distinct buffers per rank checked against the oracle with --full (-1: all of them)")
     ap.add_argument("--inflate-streams", type=int, default=1048576,
-                    help="gzip members of the inflate section (BASELINE config 4; 0: skip)")
+                    help="gzip members of the inflate section of --full (BASELINE config 4; 0: skip)")
     ap.add_argument("--inflate-distinct", type=int, default=2048, help="distinct gzip members among them")
     ap.add_argument("--inflate-order", choices=("both", "differ", "identical"), default="both",
                     help="which decode order(s) of the replicated batch to measure (profiling aid)")
@@ -497,11 +550,11 @@ def main() -> None:
                          "ranks point to point, the streams are gathered back (BASELINE config 5's wording; "
                          "reported beside the headline, never part of it)")
     ap.add_argument("--levels-64k", type=int, default=16384,
-                    help="64 KiB buffers of the level 1/6/9 section (BASELINE config 3; 0: skip)")
+                    help="64 KiB buffers of the level 1/6/9 section of --full (BASELINE config 3; 0: skip)")
     ap.add_argument("--with-inflate", action="store_true",
                     help="also time the inflate kernel on the produced streams (extra field)")
     ap.add_argument("--corpus-dir", default=os.environ.get("ZSC_CORPUS_DIR", ""),
-                    help="directory holding the real Canterbury files: compress them with max_block_len 100 000 "
+                    help="with --full, the directory holding the real Canterbury files: compress them with max_block_len 100 000 "
                          "and put the totals next to the reference's published ones (extra field)")
     ap.add_argument("--config5", type=float, default=0.0,
                     help="BASELINE config 5 instead of the headline: this many GiB (the config says 16) of 64 KiB "
@@ -509,6 +562,12 @@ def main() -> None:
     ap.add_argument("--max-block-len", type=int, default=0,
                     help="also time the same buffers as streams of sections of this length "
                          "(zsc_compress with max_block_len < source_len; extra field)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also check the streams against the oracle, time the CPU baseline "
+                         "and run the inflate, levels-64k and corpus-dir sections (a plain run does none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed as .npy files under DIR "
+                         "(rank 0's buffers; see dump_outputs)")
     args = ap.parse_args()
 
     import torch
@@ -609,6 +668,7 @@ def main() -> None:
         ktimes[k] = kt[k]
     if any(s != 0 for s in stats):
         raise SystemExit(f"rank {rank}: {sum(1 for s in stats if s)} buffers failed")
+    dumped = dump_outputs(args.dump_outputs, d_out, plan, lens, stats) if args.dump_outputs and rank == 0 else None
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
@@ -616,43 +676,44 @@ def main() -> None:
     elapsed = float(t[0])
     all_sizes = sharding.gather_sizes(lens, len(all_lens), begin, rank, world, device=dev)
 
-    # ---- parity spot check on this rank (oracle = checker only)
+    # ---- parity spot check on this rank (oracle = checker only; --full)
     from oracle.oracle_py import Oracle
-    oracle = Oracle()
-    out_host = None
-    nver = len(period_bufs) if args.verify < 0 else min(args.verify, len(period_bufs))
-    if nver:
-        from concurrent.futures import ThreadPoolExecutor
-        out_host = d_out[:plan.out_offsets[len(period_bufs) - 1] + plan.out_caps[len(period_bufs) - 1]].cpu()
-        picks = [i if nver == len(period_bufs) else (7 * i + 2) % len(period_bufs) for i in range(nver)]
+    checked = None
+    if args.full:
+        out_host = None
+        nver = len(period_bufs) if args.verify < 0 else min(args.verify, len(period_bufs))
+        if nver:
+            from concurrent.futures import ThreadPoolExecutor
+            out_host = d_out[:plan.out_offsets[len(period_bufs) - 1] + plan.out_caps[len(period_bufs) - 1]].cpu()
+            picks = [i if nver == len(period_bufs) else (7 * i + 2) % len(period_bufs) for i in range(nver)]
 
-        def check(k):  # (the checker's C code runs without the interpreter lock: one oracle per call is fine)
-            got = bytes(out_host[plan.out_offsets[k]:plan.out_offsets[k] + lens[k]].numpy())
-            rc, want, _ = Oracle().compress(period_bufs[k], args.level)
-            return k if (rc != 0 or got != want) else -1
+            def check(k):  # (the checker's C code runs without the interpreter lock: one oracle per call is fine)
+                got = bytes(out_host[plan.out_offsets[k]:plan.out_offsets[k] + lens[k]].numpy())
+                rc, want, _ = Oracle().compress(period_bufs[k], args.level)
+                return k if (rc != 0 or got != want) else -1
 
-        with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1))) as ex:
-            wrong = [k for k in ex.map(check, picks) if k >= 0]
-        if wrong:
-            raise SystemExit(f"rank {rank}: buffer {wrong[0]} differs from the oracle")
-    # the other copies: same length as, and on the device byte for byte equal to, the first copy
-    nper = len(period_bufs)
-    replicas_ok = all(lens[i] == lens[i % nper] for i in range(len(lens)))
-    if len(my_lens) > nper:
-        per_out = plan.out_offsets[nper]
-        mask = torch.zeros(per_out, dtype=torch.bool)
-        for k in range(nper):
-            mask[plan.out_offsets[k]:plan.out_offsets[k] + lens[k]] = True
-        d_mask = mask.to(dev)
-        full = len(my_lens) // nper
-        rows = d_out[:full * per_out].view(full, per_out)
-        for r0 in range(0, full, 64):  # in slices, to bound the temporary
-            replicas_ok = replicas_ok and bool((rows[r0:r0 + 64][:, d_mask] == rows[0][d_mask]).all())
-        del rows, d_mask
-    if not replicas_ok:
-        raise SystemExit(f"rank {rank}: a replica's stream differs from its first copy")
-    checked = {"distinct_buffers_vs_oracle": nver, "of": nper, "replicas_equal_on_device": bool(replicas_ok),
-               "buffers": len(my_lens)}
+            with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1))) as ex:
+                wrong = [k for k in ex.map(check, picks) if k >= 0]
+            if wrong:
+                raise SystemExit(f"rank {rank}: buffer {wrong[0]} differs from the oracle")
+        # the other copies: same length as, and on the device byte for byte equal to, the first copy
+        nper = len(period_bufs)
+        replicas_ok = all(lens[i] == lens[i % nper] for i in range(len(lens)))
+        if len(my_lens) > nper:
+            per_out = plan.out_offsets[nper]
+            mask = torch.zeros(per_out, dtype=torch.bool)
+            for k in range(nper):
+                mask[plan.out_offsets[k]:plan.out_offsets[k] + lens[k]] = True
+            d_mask = mask.to(dev)
+            full = len(my_lens) // nper
+            rows = d_out[:full * per_out].view(full, per_out)
+            for r0 in range(0, full, 64):  # in slices, to bound the temporary
+                replicas_ok = replicas_ok and bool((rows[r0:r0 + 64][:, d_mask] == rows[0][d_mask]).all())
+            del rows, d_mask
+        if not replicas_ok:
+            raise SystemExit(f"rank {rank}: a replica's stream differs from its first copy")
+        checked = {"distinct_buffers_vs_oracle": nver, "of": nper, "replicas_equal_on_device": bool(replicas_ok),
+                   "buffers": len(my_lens)}
     if staged is not None:
         out_ranges = [(r * plan.out_bytes, (r + 1) * plan.out_bytes) for r in range(world)]
         torch.cuda.synchronize()
@@ -709,7 +770,7 @@ def main() -> None:
         wall = time.perf_counter() - t1
         k = 3 % len(period_bufs)
         got = bytes(d_sec[ooff[k]:ooff[k] + slens[k]].cpu().numpy())
-        want = oracle.compress(period_bufs[k], args.level, max_block_len=mbl, dest_cap=caps[k])
+        want = Oracle().compress(period_bufs[k], args.level, max_block_len=mbl, dest_cap=caps[k])
         sections_info = {"max_block_len": mbl, "MB_per_s_in": round(in_bytes_rank / wall / 1e6, 2),
                          "wall_ms": round(wall * 1e3, 3), "compressed_bytes": sum(slens),
                          "all_ok": bool(rc == 0 and all(x == 0 for x in sstat) and (want[0], want[1]) == (0, got)),
@@ -751,9 +812,12 @@ def main() -> None:
                                  "sums over the step's launches, one per sub-batch); traffic likewise per step",
                          "kernel_ms": {k: round(v, 3) for k, v in ktimes.items()}},
             "scratch_bytes": plan.scratch_bytes,
-            "checked": checked,
             "device": zsc_amd.device_info(),
         }
+        if checked is not None:
+            line["checked"] = checked
+        if dumped:
+            line["outputs"] = dumped
         line["roofline"]["limited_by"] = ("instruction issue, not HBM: the parse is serial control flow per "
                                           "position (DESIGN.md section 5)")
         # HBM traffic of the dominant kernel from rocprofv3 --pmc passes (profiles/pmc_traffic.json),
@@ -772,11 +836,11 @@ def main() -> None:
             line["inflate_of_these_streams"] = inflate_info
         if sections_info:
             line["sections"] = sections_info
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.level)
     plan.close()
     del d_in, d_out
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the rest of BASELINE's metric, beside the headline (one GPU only: these are not sharded)
         torch.cuda.empty_cache()
         if args.inflate_streams > 0:

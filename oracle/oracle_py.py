@@ -137,6 +137,18 @@ class Reference:
                                                         mem_level, C.byref(out))
         return rc, out.value
 
+    def compress_min_work(self, window_bits, mem_level):
+        """zsc_compress_get_min_work_buf_size2 -> (rc, size)"""
+        out = C.c_uint32()
+        rc = self.lib.zsc_compress_get_min_work_buf_size2(window_bits, mem_level, C.byref(out))
+        return rc, out.value
+
+    def uncompress_min_work(self, window_bits):
+        """zsc_uncompress_get_min_work_buf_size2 -> (rc, size); size is only meaningful when rc == 0"""
+        out = C.c_uint32(12345)
+        rc = self.lib.zsc_uncompress_get_min_work_buf_size2(window_bits, C.byref(out))
+        return rc, out.value
+
     def compress(self, data: bytes, level=6, window_bits=15, mem_level=8, strategy=0,
                  max_block_len=None, dest_cap=None, work_len=COMPRESS_WORK, gz_header=None):
         """gz_header: a ctypes struct laid out like the reference's gz_header (passed by reference)"""

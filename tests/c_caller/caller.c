@@ -5,8 +5,9 @@
  * zlib_types_pub.h) plus this repo's zsc_conf_* headers (which the reference asks its
  * integrator to supply), and linked against libzsc_hip.so.  If the two disagreed about a
  * prototype, an enum's width or gz_header's layout, this is where it would show.
- * tests/c_caller/Makefile builds it where /root/reference exists; the binary travels to the GPU
- * box and tests/test_gpu_c_caller.py runs it there.
+ * oracle/Makefile (make caller_ref) builds it into oracle/_ref/ where the reference's headers
+ * exist; the binary travels with oracle/_ref/ and tests/test_gpu_c_caller.py runs it on the GPU.
+ * tests/c_caller/Makefile also builds it against this project's own include/ (caller_own).
  */
 #include <stdio.h>
 #include <stdlib.h>

@@ -29,11 +29,36 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def reference():
+def live_reference():
     from oracle.oracle_py import Reference
-    if not Reference.available():
-        pytest.skip("oracle/_ref/libzsc_ref.so not present (needs /root/reference to build)")
-    return Reference()
+    return Reference() if Reference.available() else None
+
+
+@pytest.fixture
+def reference(request, live_reference, oracle):
+    """The compiled reference where the build could make oracle/_ref/libzsc_ref.so; elsewhere its
+    recorded answers to this test's calls (tests/reference_calls.py), each restated by the oracle."""
+    if live_reference is not None:
+        yield live_reference
+        return
+    from reference_calls import RecordedReference, recorded_calls
+    calls = recorded_calls(request.node.name)
+    if calls is None:
+        pytest.fail(f"no recorded reference answers for {request.node.name}: run tests/golden/record_reference_calls.py")
+    rec = RecordedReference(calls, oracle)
+    yield rec
+    # (only where the test body passed: a failure of its own already says what went wrong)
+    rep = getattr(request.node, "rep_call", None)
+    if rep is not None and rep.passed:
+        assert rec.exhausted(), f"{request.node.name} made fewer reference calls than were recorded: re-record"
+
+
+@pytest.hookimpl(hookwrapper=True)
+def pytest_runtest_makereport(item, call):
+    """Keep each phase's report on the test item (rep_setup / rep_call), for fixture teardowns."""
+    outcome = yield
+    rep = outcome.get_result()
+    setattr(item, "rep_" + rep.when, rep)
 
 
 def gpu_available() -> bool:
