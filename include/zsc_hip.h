@@ -172,6 +172,41 @@ ZlibReturn zsc_hip_inflate_plan_results(zsc_hip_inflate_plan *plan, U32 *dest_le
                                         U32 *consumed, I32 *statuses, float *kernel_ms);
 void zsc_hip_inflate_plan_destroy(zsc_hip_inflate_plan *plan);
 
+/* Sections plans: the same arguments and plan type as zsc_hip_inflate_plan_create (_run, _results
+ * and _destroy work unchanged), for streams written with Z_FULL_FLUSH every max_block_len bytes
+ * (zsc_compress2 with max_block_len < source_len, or any encoder's full flushes).  A run first finds
+ * each stream's byte-aligned 00 00 FF FF flush markers, decodes every section between them in a
+ * lane group of its own, places the outputs at their offsets and checks the trailer by combining
+ * the sections' Adler-32 / CRC-32 (zsc_amd/csrc/inflate_sections.h); then the serial decoder runs
+ * over the plan as usual.  The parallel path only ever reports a clean Z_OK.  Every stream it cannot
+ * finish that way is decoded serially from its start, exactly as zsc_hip_inflate_plan_create's plan
+ * decodes it: a stream with no marker, a section that needs the output of an earlier one (e.g.
+ * Z_SYNC_FLUSH), a data error anywhere (with its inflateSync resynchronisation), Z_NEED_DICT,
+ * truncation, a short dest_caps[i], a trailer or ISIZE mismatch, more than source_len / 32 + 8
+ * candidate markers, a used-up candidate pool (below), or a count pass that has decoded more than 4 * source_len + 64 KiB input bytes
+ * from the stream's candidates (false markers inside stored data or a gzip header are decoded and
+ * thrown away; this bounds the work they cause; groups already decoding when the bound is reached
+ * finish their candidate).  So status, output bytes and consumed equal the plain plan's for every
+ * input.  kernel_ms of _results covers all launches of a run.  Scratch, held from create to destroy
+ * (zsc_hip_inflate_plan_scratch_bytes): 28 bytes per slot of one candidate pool of
+ * (sum of source_lens) / 256 + 65 536 slots, taken at run time only by streams that have markers
+ * (a stream that finds the pool used up is decoded serially), 16 bytes per 4 KiB of input and
+ * 100 bytes per stream. */
+ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan **plan, U32 count,
+                                                const U32 *source_lens, const uint64_t *src_offsets,
+                                                const U32 *dest_caps, const uint64_t *dst_offsets,
+                                                I32 window_bits);
+/* after _results: per stream, the number of sections decoded in parallel; 0 for streams the serial
+ * decoder produced (and for every stream of a plan that is not a sections plan) */
+ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *plan, U32 *sections);
+/* bytes of device scratch a sections plan holds beyond a plain plan's (0 for a plain plan) */
+uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_plan *plan);
+
+/* zsc_hip_uncompress_batch through a sections plan: the same signature and per-item semantics */
+ZlibReturn zsc_hip_uncompress_sections_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                             U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                             I32 window_bits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,12 @@ def _load() -> C.CDLL:
                                               u64p, C.c_int32]
     L.zsc_hip_inflate_plan_create_ordered.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p,
                                                       u64p, C.c_int32, u32p]
+    L.zsc_hip_inflate_plan_create_sections.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p,
+                                                       u64p, C.c_int32]
+    L.zsc_hip_inflate_plan_sections.argtypes = [C.c_void_p, u32p]
+    L.zsc_hip_inflate_plan_scratch_bytes.argtypes = [C.c_void_p]
+    L.zsc_hip_inflate_plan_scratch_bytes.restype = C.c_uint64
+    L.zsc_hip_uncompress_sections_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes
     L.zsc_hip_inflate_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.zsc_hip_inflate_plan_results.argtypes = [C.c_void_p, u32p, u32p, i32p, C.POINTER(C.c_float)]
     L.zsc_hip_inflate_plan_destroy.argtypes = [C.c_void_p]
@@ -315,6 +321,17 @@ def uncompress_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
                      window_bits: int = DEF_WBITS) -> Tuple[int, List[bytes], List[int], List[int]]:
     """zsc_hip_uncompress_batch: every item behaves like one zsc_uncompress2 call.
     Returns (rc, outputs, consumed, statuses)."""
+    return _uncompress_batch(lib.zsc_hip_uncompress_batch, sources, dest_caps, window_bits)
+
+
+def uncompress_sections_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
+                              window_bits: int = DEF_WBITS) -> Tuple[int, List[bytes], List[int], List[int]]:
+    """zsc_hip_uncompress_sections_batch: as uncompress_batch, with the full-flush sections of
+    each stream decoded in parallel (results identical to uncompress_batch for every input)."""
+    return _uncompress_batch(lib.zsc_hip_uncompress_sections_batch, sources, dest_caps, window_bits)
+
+
+def _uncompress_batch(fn, sources, dest_caps, window_bits):
     count = len(sources)
     srcs = (C.c_char_p * count)(*sources)
     slen = (C.c_uint32 * count)(*[len(s) for s in sources])
@@ -322,16 +339,19 @@ def uncompress_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
     dsts = (C.c_void_p * count)(*[C.addressof(b) for b in bufs])
     dlen = (C.c_uint32 * count)(*dest_caps)
     stat = (C.c_int32 * count)()
-    rc = lib.zsc_hip_uncompress_batch(count, srcs, slen, dsts, dlen, stat, window_bits)
+    rc = fn(count, srcs, slen, dsts, dlen, stat, window_bits)
     outs = [bufs[i].raw[:dlen[i]] for i in range(count)] if rc == Z_OK else []
     return rc, outs, list(slen), list(stat)
 
 
 class InflatePlan:
-    """Device-resident inflate batch (see include/zsc_hip.h)."""
+    """Device-resident inflate batch (see include/zsc_hip.h).  sections=True makes a sections plan
+    (zsc_hip_inflate_plan_create_sections: full-flush sections decoded in parallel; it takes no
+    decode_order)."""
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int],
-                 window_bits: int = DEF_WBITS, decode_order: Sequence[int] | None = None):
+                 window_bits: int = DEF_WBITS, decode_order: Sequence[int] | None = None,
+                 sections: bool = False):
         self.count = n = len(source_lens)
         so, do, sb, db = [], [], 0, 0
         for sl, dc in zip(source_lens, dest_caps):
@@ -342,10 +362,17 @@ class InflatePlan:
         self.src_offsets, self.dst_offsets = so, do
         self.src_bytes, self.dst_bytes = sb + 64, db + 64
         self._h = C.c_void_p()
-        order = None if decode_order is None else (C.c_uint32 * n)(*decode_order)
-        rc = lib.zsc_hip_inflate_plan_create_ordered(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
-                                                     (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
-                                                     (C.c_uint64 * n)(*do), window_bits, order)
+        if sections:
+            if decode_order is not None:
+                raise ValueError("a sections plan takes no decode_order")
+            rc = lib.zsc_hip_inflate_plan_create_sections(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
+                                                          (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
+                                                          (C.c_uint64 * n)(*do), window_bits)
+        else:
+            order = None if decode_order is None else (C.c_uint32 * n)(*decode_order)
+            rc = lib.zsc_hip_inflate_plan_create_ordered(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
+                                                         (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
+                                                         (C.c_uint64 * n)(*do), window_bits, order)
         if rc != Z_OK:
             raise RuntimeError(f"zsc_hip_inflate_plan_create failed: {rc}")
 
@@ -362,6 +389,19 @@ class InflatePlan:
         if rc != Z_OK:
             raise RuntimeError(f"zsc_hip_inflate_plan_results failed: {rc}")
         return list(lens), list(used), list(stat), ms.value
+
+    def sections(self) -> List[int]:
+        """After results(): per stream, the sections decoded in parallel (0: decoded serially)."""
+        n = self.count
+        out = (C.c_uint32 * max(n, 1))()
+        rc = lib.zsc_hip_inflate_plan_sections(self._h, out)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_sections failed: {rc}")
+        return list(out)[:n]
+
+    def scratch_bytes(self) -> int:
+        """Device scratch of a sections plan beyond a plain plan's (0 for a plain plan)."""
+        return int(lib.zsc_hip_inflate_plan_scratch_bytes(self._h))
 
     def close(self) -> None:
         if self._h:

@@ -251,6 +251,28 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
     return 0xffffffffu;
 }
 
+/* Section variants (inflate_sections.h): compile-time flags of inflate_stream, 0 = the whole stream
+ * as zsc_uncompress decodes it.  With any of them set the results go to *si, never to res / rs:
+ *   INF_SEC_STOP     stop after a non-final empty stored block (the 00 00 FF FF of a flush);
+ *   INF_SEC_COUNT    store nothing: output bytes are only counted (no copies at all);
+ *   INF_SEC_NOTRAIL  stop at the end of the final block and report where the trailer starts. */
+#define INF_SEC_STOP 1u
+#define INF_SEC_COUNT 2u
+#define INF_SEC_NOTRAIL 4u
+/* outcomes */
+#define INF_SEC_SYNC 1u    /* ended at a non-final empty stored block */
+#define INF_SEC_FINAL 2u   /* ended at the final block (stop = the trailer's offset) */
+#define INF_SEC_ERROR 3u   /* data error, truncation, full output, Z_NEED_DICT, bad window_bits */
+#define INF_SEC_HISTORY 4u /* a distance beyond the section's own output */
+typedef struct {
+    uint32_t outcome;
+    uint32_t stop;    /* input bytes consumed (the next section starts here) */
+    uint32_t out_len; /* output bytes */
+    uint32_t maxd;    /* the longest distance copied from */
+    uint32_t dmax;    /* the distance limit the header set */
+    uint32_t gzip;    /* the header was a gzip header */
+} InfSecInfo;
+
 /* the whole stream; mirrors zsc_uncompress_gzip2 with gz_head == NULL */
 /* One inflate() call of zsc_uncompress's loop (reference src/zsc_uncompr.c:104-125): decodes
  * until the stream ends or fails.  Returns 1 after a data error: *rs then holds what
@@ -259,7 +281,8 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
  * by a loop in here: wrapping the decoder in an outer loop doubles its register count (135
  * instead of 68 VGPRs, occupancy 3 instead of 7), and even the search alone, placed after the
  * decode loop, costs it a wave per SIMD; the sound streams would pay for the damaged ones. */
-DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume *rs)
+template <uint32_t SEC = 0u>
+DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume *rs, InfSecInfo *si = nullptr)
 {
     const uint8_t *src = job.src;
     const uint32_t n = job.n, cap = job.cap;
@@ -284,7 +307,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     LANEVAR(uint32_t, cur); /* dword GLANE of the current 256-byte input chunk */
     FOR_GLANES { LV(cur) = inf_input_dword(src, 4u * (uint32_t)GLANE, n); }
 
-    const int resumed = GUNI(rs->state) == 1u;
+    const int resumed = SEC == 0u && GUNI(rs->state) == 1u;
     uint32_t pos = 0; /* output bytes produced (each is stored to dst as it is made) */
     uint32_t dmax = 32768u;
     int gzip = 0;
@@ -295,6 +318,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     uint64_t sy_start = 0;    /* at a data error: where the reference's bit buffer starts (bit offset) */
     uint32_t sy_rb = 0;       /* ... and how many bits it holds */
     uint32_t fail_line = 0; /* source line of the check that rejected the stream (diagnostics) */
+    uint32_t sec_maxd = 0, sec_hist = 0, sec_sync = 0; /* (section variants only) */
+    (void)sec_maxd;
+    (void)sec_hist;
+    (void)sec_sync;
 
 /* top up the bit buffer to at least 32 bits (or to the end of the input) */
 #define INF_REFILL()                                                                          \
@@ -610,6 +637,9 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                 short_out = 1;
             }
             /* 256 bytes per step, into the output and the ring */
+            if constexpr ((SEC & INF_SEC_COUNT) != 0u) /* (count variant: no copy; the loop below is unindented to keep its diff empty) */
+                pos += can;
+            else
             for (uint32_t k = 0; k < can; k += 256u) {
                 const uint32_t step = can - k < 256u ? can - k : 256u;
                 FOR_GLANES
@@ -628,6 +658,13 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
             if (short_in || short_out) {
                 rc = INF_BUF; /* COPY state leaves with nothing more to do, src/inflate.c:1037-1039 */
                 goto done;
+            }
+            if constexpr ((SEC & INF_SEC_STOP) != 0u) {
+                if (len == 0 && !last) {
+                    sec_sync = 1;
+                    rc = INF_END;
+                    goto done;
+                }
             }
         } else {
             if (type == 1) {
@@ -777,12 +814,14 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                         break;
                     if (pos >= cap)
                         INF_ON_FULL;
-                    ON_GLANE0
-                    {
-                        lds->stage[pos & (INF_STAGE - 1)] = (uint8_t)sym;
-                        dst[pos] = (uint8_t)sym;
+                    if constexpr ((SEC & INF_SEC_COUNT) == 0u) {
+                        ON_GLANE0
+                        {
+                            lds->stage[pos & (INF_STAGE - 1)] = (uint8_t)sym;
+                            dst[pos] = (uint8_t)sym;
+                        }
+                        WAVE_SYNC();
                     }
-                    WAVE_SYNC();
                     pos++;
                 }
                 if (sym == 256)
@@ -815,9 +854,13 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                         INF_BAD;
                     if (pos >= cap) /* MATCH leaves on a full output before it looks at the distance (:1277) */
                         INF_ON_FULL;
+                    if constexpr (SEC != 0u)
+                        sec_hist = 1; /* (a section: the bytes lie in an earlier one) */
                     INF_BAD; /* :1279-1288; nothing behind an inflateSync can be copied */
                 }
                 INF_TAKE(ex, xb);
+                if constexpr (SEC != 0u)
+                    sec_maxd = dist > sec_maxd ? dist : sec_maxd;
                 uint32_t can = len;
                 if (can > cap - pos)
                     can = cap - pos;
@@ -827,6 +870,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                  * far more than the error of the reciprocal -- a handful of instructions where the
                  * integer division is ~30 */
                 const float rdist = RCP_F32((float)dist);
+                if constexpr ((SEC & INF_SEC_COUNT) == 0u)
                 for (uint32_t k = 0; k < can; k += GRP) {
                     FOR_GLANES
                     {
@@ -885,6 +929,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
         uint32_t t;
         INF_TAKE(t, br.bits & 7u);
         (void)t;
+        if constexpr ((SEC & INF_SEC_NOTRAIL) != 0u) {
+            rc = INF_END; /* (the trailer is checked by whoever put the sections together) */
+            goto done;
+        }
         if (wrap) {
             uint32_t v;
             INF_NEED(32);
@@ -910,6 +958,19 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     }
 
 bad:
+    if constexpr (SEC != 0u) {
+        ON_GLANE0
+        {
+            si->outcome = sec_hist ? INF_SEC_HISTORY : INF_SEC_ERROR;
+            si->stop = (uint32_t)((BR_USED + 7u) >> 3);
+            si->out_len = pos;
+            si->maxd = sec_maxd;
+            si->dmax = dmax;
+            si->gzip = (uint32_t)gzip;
+        }
+        WAVE_SYNC();
+        return 0;
+    }
     /* a data error: hand the state inflateSync starts from to the next entry */
     data_errors++;
     ON_GLANE0
@@ -926,6 +987,22 @@ bad:
     return 1;
 
 done:
+    if constexpr (SEC != 0u) {
+        ON_GLANE0
+        {
+            uint32_t used_bytes = (uint32_t)((BR_USED + 7u) >> 3);
+            if (exhausted || used_bytes > n)
+                used_bytes = n;
+            si->outcome = rc != INF_END ? INF_SEC_ERROR : sec_sync ? INF_SEC_SYNC : INF_SEC_FINAL;
+            si->stop = used_bytes;
+            si->out_len = pos;
+            si->maxd = sec_maxd;
+            si->dmax = dmax;
+            si->gzip = (uint32_t)gzip;
+        }
+        WAVE_SYNC();
+        return 0;
+    }
     ON_GLANE0
     {
         uint32_t used_bytes = (uint32_t)((BR_USED + 7u) >> 3);

@@ -25,6 +25,7 @@
 #include "hash_sort.h"
 #include "huff_plan.h"
 #include "inflate.h"
+#include "inflate_sections.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "match_table.h"
@@ -618,6 +619,60 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU
                 atomicAdd(pending, 1u); /* the host launches once more for these */
         }
     }
+}
+
+/* kernel 6 (inflate_sections.h): the full-flush sections of each stream inflated in parallel, in
+ * six launches ahead of k_inflate */
+__global__ __launch_bounds__(64) void k_sec_scan(const uint8_t *__restrict__ src, IsecPlan P, int write)
+{
+    for (uint32_t t = blockIdx.x; t < P.ntiles; t += gridDim.x)
+        sec_scan_tile(P, src, t, write);
+}
+
+__global__ __launch_bounds__(64) void k_sec_setup(IsecPlan P)
+{
+    const uint32_t na = UNI(*P.q);
+    for (uint32_t a = blockIdx.x; a < na; a += gridDim.x)
+        sec_setup(P, a);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_sec_count(
+    const uint8_t *__restrict__ src, IsecPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    sec_count_worker(P, src, &lds_all[grp], &info[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_sec_resolve(IsecPlan P)
+{
+    const uint32_t na = *P.q;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
+        sec_resolve(P, a);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_sec_write(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, IsecPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    sec_write_worker(P, src, dst, &lds_all[grp], &info[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_sec_finish(const uint8_t *__restrict__ src, IsecPlan P,
+                                                   InfResult *__restrict__ res, InfResume *__restrict__ resume)
+{
+    const uint32_t na = *P.q;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
+        sec_finish(P, src, res, resume, a);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -2297,6 +2352,12 @@ struct zsc_hip_inflate_plan {
     uint32_t count = 0;
     int32_t window_bits = 15;
     DevBuf d_items, d_order, d_res, d_resume, d_pending;
+    /* sections plans only (inflate_sections.h) */
+    bool sections = false;
+    IsecPlan sp = {};
+    uint64_t ncand_total = 0, scratch_bytes = 0;
+    DevBuf d_sitems, d_tiles, d_tile_cnt, d_tile_off, d_scount, d_nsec, d_sst, d_active, d_q;
+    DevBuf d_cstart, d_cstop, d_clink, d_clen, d_chain_k, d_chain_off, d_chain_ck;
     const void *last_src = nullptr;
     void *last_dst = nullptr;
     hipStream_t last_stream = nullptr;
@@ -2385,6 +2446,116 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create(zsc_hip_inflate_plan **plan_ou
                                                window_bits, Z_NULL);
 }
 
+static void inflate_plan_release(zsc_hip_inflate_plan *pl)
+{
+    for (DevBuf *b : {&pl->d_items, &pl->d_order, &pl->d_res, &pl->d_resume, &pl->d_pending, &pl->d_sitems,
+                      &pl->d_tiles, &pl->d_tile_cnt, &pl->d_tile_off, &pl->d_scount, &pl->d_nsec, &pl->d_sst,
+                      &pl->d_active, &pl->d_q, &pl->d_cstart, &pl->d_cstop, &pl->d_clink, &pl->d_clen,
+                      &pl->d_chain_k, &pl->d_chain_off, &pl->d_chain_ck})
+        b->release();
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                           const U32 *source_lens,
+                                                           const uint64_t *src_offsets,
+                                                           const U32 *dest_caps,
+                                                           const uint64_t *dst_offsets, I32 window_bits)
+{
+    ZlibReturn rc = zsc_hip_inflate_plan_create(plan_out, count, source_lens, src_offsets, dest_caps, dst_offsets,
+                                                window_bits);
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    zsc_hip_inflate_plan *pl = *plan_out;
+    pl->sections = true;
+    /* per stream: its tiles of SEC_TILE input bytes; candidate records from one pool */
+    std::vector<IsecItem> items(count);
+    std::vector<IsecTile> tiles;
+    uint64_t total_in = 0;
+    for (U32 i = 0; i < count; i++) {
+        IsecItem &it = items[i];
+        it.src_off = src_offsets[i];
+        it.dst_off = dst_offsets[i];
+        it.src_len = source_lens[i];
+        it.dst_cap = dest_caps[i];
+        it.cap = source_lens[i] / SEC_CAND_DIV + SEC_CAND_MIN;
+        it.tile0 = (uint32_t)tiles.size();
+        it.ntiles = (source_lens[i] + SEC_TILE - 1u) / SEC_TILE;
+        it.pad = 0;
+        for (uint32_t t = 0; t < it.ntiles; t++)
+            tiles.push_back(IsecTile{i, t * SEC_TILE});
+        total_in += source_lens[i];
+    }
+    const uint64_t cand = std::min<uint64_t>(SEC_POOL_SLOTS(total_in), 0x0ffffff0u);
+    if (tiles.size() >= 0xffffffffull) {
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    const uint64_t nt = std::max<uint64_t>(1, tiles.size()), nc = std::max<uint64_t>(1, count);
+    pl->ncand_total = cand;
+    bool ok = pl->d_sitems.ensure(sizeof(IsecItem) * nc) && pl->d_tiles.ensure(sizeof(IsecTile) * nt) &&
+              pl->d_tile_cnt.ensure(4 * nt) && pl->d_tile_off.ensure(4 * nt) && pl->d_scount.ensure(4 * nc) &&
+              pl->d_nsec.ensure(4 * nc) && pl->d_sst.ensure(sizeof(IsecStream) * nc) &&
+              pl->d_active.ensure(4 * nc) && pl->d_q.ensure(16) && pl->d_cstart.ensure(4 * cand) &&
+              pl->d_cstop.ensure(4 * cand) && pl->d_clink.ensure(4 * cand) && pl->d_clen.ensure(4 * cand) &&
+              pl->d_chain_k.ensure(4 * cand) && pl->d_chain_off.ensure(4 * cand) && pl->d_chain_ck.ensure(4 * cand);
+    if (ok && count)
+        ok = hipMemcpy(pl->d_sitems.p, items.data(), sizeof(IsecItem) * count, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !tiles.empty())
+        ok = hipMemcpy(pl->d_tiles.p, tiles.data(), sizeof(IsecTile) * tiles.size(), hipMemcpyHostToDevice) ==
+             hipSuccess;
+    if (!ok) {
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    IsecPlan &P = pl->sp;
+    P.items = (const IsecItem *)pl->d_sitems.p;
+    P.tiles = (const IsecTile *)pl->d_tiles.p;
+    P.tile_cnt = (uint32_t *)pl->d_tile_cnt.p;
+    P.tile_off = (uint32_t *)pl->d_tile_off.p;
+    P.scount = (uint32_t *)pl->d_scount.p;
+    P.nsec = (uint32_t *)pl->d_nsec.p;
+    P.st = (IsecStream *)pl->d_sst.p;
+    P.active = (uint32_t *)pl->d_active.p;
+    P.q = (uint32_t *)pl->d_q.p;
+    P.cstart = (uint32_t *)pl->d_cstart.p;
+    P.cstop = (uint32_t *)pl->d_cstop.p;
+    P.clink = (uint32_t *)pl->d_clink.p;
+    P.clen = (uint32_t *)pl->d_clen.p;
+    P.chain_k = (uint32_t *)pl->d_chain_k.p;
+    P.chain_off = (uint32_t *)pl->d_chain_off.p;
+    P.chain_ck = (uint32_t *)pl->d_chain_ck.p;
+    P.count = count;
+    P.ntiles = (uint32_t)tiles.size();
+    P.pool = (uint32_t)cand;
+    P.window_bits = window_bits;
+    P.work_mul = SEC_WORK_MUL;
+    P.work_add = SEC_WORK_ADD;
+    pl->scratch_bytes = sizeof(IsecItem) * nc + (sizeof(IsecTile) + 8) * nt +
+                        (8 + sizeof(IsecStream) + 4) * nc + 16 + 28 * cand;
+    return Z_OK;
+}
+
+/* the six launches of a sections plan, ahead of k_inflate */
+static void sec_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
+{
+    const IsecPlan &P = pl->sp;
+    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU; /* wavefronts that fill the device */
+    const uint32_t per_stream = std::max(1u, std::min(pl->count, fill));
+    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
+    const uint32_t tiles = std::max(1u, std::min(P.ntiles, fill * 4u));
+    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 0);
+    hipLaunchKernelGGL(k_sec_setup, dim3(per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 1);
+    hipLaunchKernelGGL(k_sec_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_sec_resolve, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_sec_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P);
+    hipLaunchKernelGGL(k_sec_finish, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
+                       (const uint8_t *)d_src, P, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+}
+
 extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const void *d_src,
                                                void *d_dst, void *hip_stream)
 {
@@ -2399,7 +2570,14 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
     pl->last_dst = d_dst;
     HIP_TRY(hipMemsetAsync(pl->d_resume.p, 0, sizeof(InfResume) * pl->count, st), return Z_STREAM_ERROR);
     HIP_TRY(hipMemsetAsync(pl->d_pending.p, 0, 8, st), return Z_STREAM_ERROR); /* [0] streams to relaunch, [1] the queue */
+    if (pl->sections) {
+        HIP_TRY(hipMemsetAsync(pl->d_scount.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+        HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+        HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
+    }
     (void)hipEventRecord(pl->ev0, st);
+    if (pl->sections)
+        sec_enqueue(pl, d_src, d_dst, st);
     hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, st, (const uint8_t *)d_src,
                        (uint8_t *)d_dst, (const ZdInfItem *)pl->d_items.p,
                        (const uint32_t *)pl->d_order.p, (InfResult *)pl->d_res.p,
@@ -2462,11 +2640,7 @@ extern "C" void zsc_hip_inflate_plan_destroy(zsc_hip_inflate_plan *pl)
     if (!pl)
         return;
     (void)hipStreamSynchronize(pl->last_stream);
-    pl->d_items.release();
-    pl->d_order.release();
-    pl->d_res.release();
-    pl->d_resume.release();
-    pl->d_pending.release();
+    inflate_plan_release(pl);
     if (pl->ev0)
         (void)hipEventDestroy(pl->ev0);
     if (pl->ev1)
@@ -2474,10 +2648,46 @@ extern "C" void zsc_hip_inflate_plan_destroy(zsc_hip_inflate_plan *pl)
     delete pl;
 }
 
+extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U32 *sections)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(sections != Z_NULL);
+    if (!pl->sections || !pl->last_dst || pl->count == 0) {
+        for (uint32_t i = 0; i < pl->count; i++)
+            sections[i] = 0;
+        return Z_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+    HIP_TRY(hipMemcpy(sections, pl->d_nsec.p, 4ull * pl->count, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    return Z_OK;
+}
+
+extern "C" uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_plan *pl)
+{
+    return pl ? pl->scratch_bytes : 0;
+}
+
+static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
+                                        U32 *dest_lens, I32 *statuses, I32 window_bits, bool sections);
+
 /* host-pointer batch: stage through one pair of device buffers */
 extern "C" ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources,
                                                U32 *source_lens, U8 *const *dests,
                                                U32 *dest_lens, I32 *statuses, I32 window_bits)
+{
+    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, false);
+}
+
+extern "C" ZlibReturn zsc_hip_uncompress_sections_batch(U32 count, const U8 *const *sources,
+                                                        U32 *source_lens, U8 *const *dests,
+                                                        U32 *dest_lens, I32 *statuses, I32 window_bits)
+{
+    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, true);
+}
+
+static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
+                                        U32 *dest_lens, I32 *statuses, I32 window_bits, bool sections)
 {
     DeviceScope scope;
     ZSC_ASSERT(sources != Z_NULL);
@@ -2497,8 +2707,10 @@ extern "C" ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sourc
         db += ((uint64_t)dest_lens[i] + 64u + 15u) & ~15ull;
     }
     zsc_hip_inflate_plan *pl = nullptr;
-    ZlibReturn rc = zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_lens,
-                                                dof.data(), window_bits);
+    ZlibReturn rc = sections ? zsc_hip_inflate_plan_create_sections(&pl, count, source_lens, so.data(), dest_lens,
+                                                                    dof.data(), window_bits)
+                             : zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_lens,
+                                                           dof.data(), window_bits);
     if (rc != Z_OK)
         return rc;
     DevBuf d_src, d_dst;
