@@ -196,16 +196,45 @@ ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan **plan, U32
                                                 const U32 *source_lens, const uint64_t *src_offsets,
                                                 const U32 *dest_caps, const uint64_t *dst_offsets,
                                                 I32 window_bits);
-/* after _results: per stream, the number of sections decoded in parallel; 0 for streams the serial
- * decoder produced (and for every stream of a plan that is not a sections plan) */
+/* after _results: per stream, the number of sections (or pieces, of a chunks plan) decoded in parallel;
+ * 0 for streams the serial decoder produced (and for every stream of a plain plan) */
 ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *plan, U32 *sections);
-/* bytes of device scratch a sections plan holds beyond a plain plan's (0 for a plain plan) */
+/* bytes of device scratch a sections or chunks plan holds beyond a plain plan's (0 for a plain plan) */
 uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_plan *plan);
 
 /* zsc_hip_uncompress_batch through a sections plan: the same signature and per-item semantics */
 ZlibReturn zsc_hip_uncompress_sections_batch(U32 count, const U8 *const *sources, U32 *source_lens,
                                              U8 *const *dests, U32 *dest_lens, I32 *statuses,
                                              I32 window_bits);
+
+/* Chunks plans: the arguments of zsc_hip_inflate_plan_create_sections plus chunk_bytes, the compressed
+ * bytes per piece the plan aims at (0: the default, 128 KiB, chosen from a sweep over 32 KiB to 1 MiB
+ * on one 1 GiB-output stream; values below 4 KiB are taken as 4 KiB).  For any stream, whoever
+ * wrote it: each stream longer than chunk_bytes (with dest_caps[i] < 2 GiB) is cut into chunks of
+ * chunk_bytes input bytes; a run finds candidate block starts in each chunk by trial (dynamic-Huffman
+ * headers at any bit offset, ends of stored blocks), decodes from them with placeholders for the
+ * unknown window before each piece, chains the pieces from the stream's start, passes the 32 KiB
+ * windows from piece to piece and decodes every chained piece again into place
+ * (zsc_amd/csrc/inflate_chunks.h); then the serial decoder runs over the plan as usual.  _run,
+ * _results, _destroy, zsc_hip_inflate_plan_sections (pieces decoded in parallel per stream, 0 for
+ * serial) and zsc_hip_inflate_plan_scratch_bytes work on it.  As with sections plans the parallel path
+ * only ever reports a clean Z_OK; every stream it cannot finish that way -- a data error anywhere,
+ * Z_NEED_DICT, truncation, a short dest_caps[i], a trailer or ISIZE mismatch, a chain broken by a
+ * missed or false candidate, a reach before the output or beyond the header's window, a count pass
+ * that has decoded more than 4 * source_len + 64 KiB input bytes -- is decoded serially from its
+ * start, so status, output bytes and consumed equal the plain plan's for every input.  Scratch, held
+ * from create to destroy: 98 372 bytes per chunk of the streams longer than chunk_bytes (a 64 KiB
+ * ring of 16-bit symbols, a 32 KiB window, 32 bytes of candidates, 36 bytes of records), 8 bytes per
+ * chunk after a stream's first, and 96 bytes per stream plus 16. */
+ZlibReturn zsc_hip_inflate_plan_create_chunks(zsc_hip_inflate_plan **plan, U32 count,
+                                              const U32 *source_lens, const uint64_t *src_offsets,
+                                              const U32 *dest_caps, const uint64_t *dst_offsets,
+                                              I32 window_bits, U32 chunk_bytes);
+/* zsc_hip_uncompress_batch through a chunks plan (default chunk_bytes): the same signature and
+ * per-item semantics */
+ZlibReturn zsc_hip_uncompress_chunks_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                           U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                           I32 window_bits);
 
 #ifdef __cplusplus
 }

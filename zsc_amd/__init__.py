@@ -7,6 +7,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
   meaning and ``ZlibReturn`` codes;
 * :func:`compress_batch` -- many independent buffers per call;
 * :func:`uncompress_sections_batch` -- the full-flush sections of each stream inflated in parallel;
+* :func:`uncompress_chunks_batch` -- any long stream inflated in parallel pieces from block starts
+  found by trial;
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -18,6 +20,7 @@ from .api import (  # noqa: F401
     compress_get_min_work_buf_size, compress_get_max_output_size, compress_get_max_output_size2,
     uncompress_get_min_work_buf_size,
     compress, compress2, compress_gzip, uncompress, uncompress2, uncompress_gzip,
-    compress_batch, compress_sections_batch, compress_sections_device, uncompress_batch, uncompress_sections_batch, DeflatePlan, InflatePlan,
+    compress_batch, compress_sections_batch, compress_sections_device, uncompress_batch, uncompress_sections_batch,
+    uncompress_chunks_batch, DeflatePlan, InflatePlan,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

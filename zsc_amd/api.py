@@ -81,6 +81,9 @@ def _load() -> C.CDLL:
     L.zsc_hip_inflate_plan_scratch_bytes.argtypes = [C.c_void_p]
     L.zsc_hip_inflate_plan_scratch_bytes.restype = C.c_uint64
     L.zsc_hip_uncompress_sections_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes
+    L.zsc_hip_inflate_plan_create_chunks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p, u64p,
+                                                     C.c_int32, C.c_uint32]
+    L.zsc_hip_uncompress_chunks_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes
     L.zsc_hip_inflate_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.zsc_hip_inflate_plan_results.argtypes = [C.c_void_p, u32p, u32p, i32p, C.POINTER(C.c_float)]
     L.zsc_hip_inflate_plan_destroy.argtypes = [C.c_void_p]
@@ -331,6 +334,14 @@ def uncompress_sections_batch(sources: Sequence[bytes], dest_caps: Sequence[int]
     return _uncompress_batch(lib.zsc_hip_uncompress_sections_batch, sources, dest_caps, window_bits)
 
 
+def uncompress_chunks_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
+                            window_bits: int = DEF_WBITS):
+    """zsc_hip_uncompress_chunks_batch: as uncompress_batch, with every stream longer than a chunk
+    decoded in parallel pieces from block starts found by trial (results identical to uncompress_batch
+    for every input)."""
+    return _uncompress_batch(lib.zsc_hip_uncompress_chunks_batch, sources, dest_caps, window_bits)
+
+
 def _uncompress_batch(fn, sources, dest_caps, window_bits):
     count = len(sources)
     srcs = (C.c_char_p * count)(*sources)
@@ -347,11 +358,13 @@ def _uncompress_batch(fn, sources, dest_caps, window_bits):
 class InflatePlan:
     """Device-resident inflate batch (see include/zsc_hip.h).  sections=True makes a sections plan
     (zsc_hip_inflate_plan_create_sections: full-flush sections decoded in parallel; it takes no
-    decode_order)."""
+    decode_order).  chunks=True makes a chunks plan (zsc_hip_inflate_plan_create_chunks: any stream longer
+    than chunk_bytes decoded in parallel pieces; chunk_bytes 0 = the library's default; no decode_order
+    either)."""
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int],
                  window_bits: int = DEF_WBITS, decode_order: Sequence[int] | None = None,
-                 sections: bool = False):
+                 sections: bool = False, chunks: bool = False, chunk_bytes: int = 0):
         self.count = n = len(source_lens)
         so, do, sb, db = [], [], 0, 0
         for sl, dc in zip(source_lens, dest_caps):
@@ -362,7 +375,15 @@ class InflatePlan:
         self.src_offsets, self.dst_offsets = so, do
         self.src_bytes, self.dst_bytes = sb + 64, db + 64
         self._h = C.c_void_p()
-        if sections:
+        if sections and chunks:
+            raise ValueError("a plan is a sections plan or a chunks plan, not both")
+        if chunks:
+            if decode_order is not None:
+                raise ValueError("a chunks plan takes no decode_order")
+            rc = lib.zsc_hip_inflate_plan_create_chunks(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
+                                                        (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
+                                                        (C.c_uint64 * n)(*do), window_bits, chunk_bytes)
+        elif sections:
             if decode_order is not None:
                 raise ValueError("a sections plan takes no decode_order")
             rc = lib.zsc_hip_inflate_plan_create_sections(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
@@ -391,7 +412,8 @@ class InflatePlan:
         return list(lens), list(used), list(stat), ms.value
 
     def sections(self) -> List[int]:
-        """After results(): per stream, the sections decoded in parallel (0: decoded serially)."""
+        """After results(): per stream, the sections (or pieces, of a chunks plan) decoded in parallel
+        (0: decoded serially)."""
         n = self.count
         out = (C.c_uint32 * max(n, 1))()
         rc = lib.zsc_hip_inflate_plan_sections(self._h, out)
@@ -400,7 +422,7 @@ class InflatePlan:
         return list(out)[:n]
 
     def scratch_bytes(self) -> int:
-        """Device scratch of a sections plan beyond a plain plan's (0 for a plain plan)."""
+        """Device scratch of a sections or chunks plan beyond a plain plan's (0 for a plain plan)."""
         return int(lib.zsc_hip_inflate_plan_scratch_bytes(self._h))
 
     def close(self) -> None:

@@ -154,6 +154,32 @@ DEV uint32_t inf_input_dword(const uint8_t *src, uint32_t a, uint32_t n)
 #define INF_CHUNK (4u * GRP) /* input bytes held across the lanes of the group */
 #define INF_SLOTS (GRP >= 16 ? 1 : 2) /* code lengths a lane tests: l, and l + GRP in a group of 8 */
 
+/* The validity rule of a set of code lengths (src/inftrees.c:168-177), from the number of codes of
+ * each length 1..15 and the longest length max (0: no codes): 0, or -1 when the set is
+ * over-subscribed, or incomplete where that is not allowed -- always for the code-length code (kind
+ * 0), and for the literal/length (1) and distance (2) codes unless the set is a single 1-bit code.
+ * inf_build and the block-start scan of inflate_chunks.h both decide with it, so they cannot disagree. */
+DEV int inf_count_verdict(const uint16_t *count, int max, int kind)
+{
+    if (max == 0)
+        return 0;
+    int left = 1;
+    for (int l = 1; l <= 15; l++) {
+        left <<= 1;
+        left -= count[l];
+        if (left < 0)
+            return -1;
+    }
+    return left > 0 && (kind == 0 || max != 1) ? -1 : 0;
+}
+/* the other rules of a dynamic block header, also shared with the scan: the ranges of HLIT and HDIST
+ * (src/inflate.c:1062-1068), a repeat (code 16) with no length before it, a repeat past HLIT + HDIST
+ * (:1116-1139), and a zero length for code 256 (:1147-1151) */
+#define INF_HDR_COUNTS_BAD(nlen, ndist) ((nlen) > 286u || (ndist) > 30u)
+#define INF_HDR_REP16_BAD(have) ((have) == 0u)
+#define INF_HDR_REP_OVERRUN(have, rep, total) ((have) + (rep) > (total))
+#define INF_HDR_EOB_BAD(len256) ((len256) == 0u)
+
 /* build a canonical decoder from code lengths.  kind 0: code-length code, 1: literal/
  * length, 2: distance.  Returns 0, or -1 for an invalid set (src/inftrees.c:168-177). */
 template <class CT>
@@ -172,17 +198,7 @@ DEV int inf_build(CT *c, const uint8_t *lens, int n, int kind)
         c->max_len = (uint32_t)max;
         c->empty = max == 0;
         if (max != 0) {
-            int left = 1;
-            for (int l = 1; l <= 15; l++) {
-                left <<= 1;
-                left -= c->count[l];
-                if (left < 0) {
-                    rc = -1;
-                    break;
-                }
-            }
-            if (rc == 0 && left > 0 && (kind == 0 || max != 1))
-                rc = -1;
+            rc = inf_count_verdict(c->count, max, kind);
             if (rc == 0) {
                 uint32_t code = 0, idx = 0;
                 for (int l = 1; l <= 15; l++) {
@@ -259,6 +275,21 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
 #define INF_SEC_STOP 1u
 #define INF_SEC_COUNT 2u
 #define INF_SEC_NOTRAIL 4u
+/* piece variants (inflate_chunks.h), with an InfPiece *pc:
+ *   INF_SEC_BITSTART start pc->skip bits into job.src, and stop at the first block boundary that is
+ *                    a candidate of a later chunk than pc->chunk (outcome INF_SEC_SYNC, pc->link);
+ *   INF_SEC_SYM16    output 16-bit symbols to the ring pc->ring (position p at p mod INF_WIN), nothing to
+ *                    dst: a byte, or INF_PH | i for a reference to byte i of the unknown window;
+ *   INF_SEC_EXTWIN   a reference before the start reads the window pc->win.
+ * In both output modes a distance beyond the piece's own output is no error: the deepest such
+ * reach goes to pc->reach and is checked by whoever puts the pieces together. */
+#define INF_SEC_BITSTART 8u
+#define INF_SEC_SYM16 16u
+#define INF_SEC_EXTWIN 32u
+#define INF_WIN 32768u   /* window entries: win[INF_WIN - d] is the byte d before the piece */
+#define INF_PH 0x8000u   /* a placeholder symbol of the 16-bit output */
+#define INF_PC_CANDS 4u  /* candidates per chunk */
+#define INF_PC_NONE 0xffffffffffffffffull
 /* outcomes */
 #define INF_SEC_SYNC 1u    /* ended at a non-final empty stored block */
 #define INF_SEC_FINAL 2u   /* ended at the final block (stop = the trailer's offset) */
@@ -273,6 +304,22 @@ typedef struct {
     uint32_t gzip;    /* the header was a gzip header */
 } InfSecInfo;
 
+typedef struct {
+    /* in */
+    uint64_t base_bit;    /* stream bit offset of job.src[0] */
+    uint64_t chunk_bits;  /* 8 * chunk_bytes */
+    const uint64_t *cand; /* the stream's candidates (bit offsets), INF_PC_CANDS per chunk */
+    uint16_t *ring;       /* INF_SEC_SYM16: INF_WIN entries */
+    const uint8_t *win;   /* INF_SEC_EXTWIN: INF_WIN bytes */
+    uint32_t skip;        /* bits of job.src[0] before the start */
+    uint32_t chunk, nchunks;
+    /* out */
+    uint32_t link;        /* chunk * INF_PC_CANDS + index of the candidate the piece stopped at */
+    uint32_t reach;       /* the farthest reference before the start, in bytes */
+    uint32_t hdr_ok;      /* the first block was a dynamic block and its header passed */
+    uint64_t end_bit;     /* stream bit offset where the piece stopped */
+} InfPiece;
+
 /* the whole stream; mirrors zsc_uncompress_gzip2 with gz_head == NULL */
 /* One inflate() call of zsc_uncompress's loop (reference src/zsc_uncompr.c:104-125): decodes
  * until the stream ends or fails.  Returns 1 after a data error: *rs then holds what
@@ -282,8 +329,10 @@ typedef struct {
  * instead of 68 VGPRs, occupancy 3 instead of 7), and even the search alone, placed after the
  * decode loop, costs it a wave per SIMD; the sound streams would pay for the damaged ones. */
 template <uint32_t SEC = 0u>
-DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume *rs, InfSecInfo *si = nullptr)
+DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume *rs, InfSecInfo *si = nullptr,
+                      InfPiece *pc = nullptr)
 {
+    constexpr bool PIECE_OUT = (SEC & (INF_SEC_SYM16 | INF_SEC_EXTWIN)) != 0u;
     const uint8_t *src = job.src;
     const uint32_t n = job.n, cap = job.cap;
     uint8_t *dst = job.dst;
@@ -322,6 +371,31 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     (void)sec_maxd;
     (void)sec_hist;
     (void)sec_sync;
+    /* (piece variants only) */
+    uint64_t pc_base = 0, pc_cbits = 1;
+    uint32_t pc_chunk = 0, pc_nch = 0, pc_link = 0xffffffffu, pc_reach = 0, pc_hdr = 0, pc_blocks = 0;
+    uint16_t *pc_ring = nullptr;
+    const uint8_t *pc_win = nullptr;
+    if constexpr ((SEC & INF_SEC_BITSTART) != 0u) {
+        pc_base = pc->base_bit;
+        pc_cbits = pc->chunk_bits;
+        pc_chunk = GUNI(pc->chunk);
+        pc_nch = GUNI(pc->nchunks);
+    }
+    if constexpr ((SEC & INF_SEC_SYM16) != 0u)
+        pc_ring = pc->ring;
+    if constexpr ((SEC & INF_SEC_EXTWIN) != 0u)
+        pc_win = pc->win;
+    (void)pc_base;
+    (void)pc_cbits;
+    (void)pc_chunk;
+    (void)pc_nch;
+    (void)pc_link;
+    (void)pc_reach;
+    (void)pc_hdr;
+    (void)pc_blocks;
+    (void)pc_ring;
+    (void)pc_win;
 
 /* top up the bit buffer to at least 32 bits (or to the end of the input) */
 #define INF_REFILL()                                                                          \
@@ -607,6 +681,16 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
         }
     }
 
+    if constexpr ((SEC & INF_SEC_BITSTART) != 0u) {
+        const uint32_t sk = GUNI(pc->skip);
+        if (sk) {
+            uint32_t t;
+            INF_NEED(sk);
+            INF_TAKE(t, sk);
+            (void)t;
+        }
+    }
+
     /* blocks */
     for (;;) {
         uint32_t last, type;
@@ -639,7 +723,15 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
             /* 256 bytes per step, into the output and the ring */
             if constexpr ((SEC & INF_SEC_COUNT) != 0u) /* (count variant: no copy; the loop below is unindented to keep its diff empty) */
                 pos += can;
-            else
+            else if constexpr ((SEC & INF_SEC_SYM16) != 0u) {
+                FOR_GLANES
+                {
+                    for (uint32_t j = (uint32_t)GLANE; j < can; j += GRP)
+                        pc_ring[(pos + j) & (INF_WIN - 1u)] = src[at + j];
+                }
+                WAVE_SYNC();
+                pos += can;
+            } else
             for (uint32_t k = 0; k < can; k += 256u) {
                 const uint32_t step = can - k < 256u ? can - k : 256u;
                 FOR_GLANES
@@ -691,7 +783,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                 nlen += 257;
                 ndist += 1;
                 ncode += 4;
-                if (nlen > 286 || ndist > 30)
+                if (INF_HDR_COUNTS_BAD(nlen, ndist))
                     INF_BAD;
                 FOR_GLANES
                 {
@@ -724,7 +816,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                     uint32_t rep, val = 0;
                     if (sym == 16) {
                         INF_NEED(2);
-                        if (have == 0) {
+                        if (INF_HDR_REP16_BAD(have)) {
                             /* NEEDBITS(here.bits + 2) may have pulled one byte more (:1116-1123) */
                             const uint32_t padb = (8u - (uint32_t)(BR_USED & 7u)) & 7u;
                             INF_BADX(0, padb >= 2u ? padb : padb + 8u);
@@ -741,7 +833,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                         INF_TAKE(rep, 7);
                         rep += 11;
                     }
-                    if (have + rep > nlen + ndist)
+                    if (INF_HDR_REP_OVERRUN(have, rep, nlen + ndist))
                         INF_BAD;
                     FOR_GLANES
                     {
@@ -751,12 +843,14 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                     WAVE_SYNC();
                     have += rep;
                 }
-                if (lds->lens[256] == 0)
+                if (INF_HDR_EOB_BAD(lds->lens[256]))
                     INF_BAD;
                 if (inf_build(&lds->lit, lds->lens, (int)nlen, 1))
                     INF_BAD;
                 if (inf_build(&lds->dist, lds->lens + nlen, (int)ndist, 2))
                     INF_BAD;
+                if constexpr ((SEC & INF_SEC_BITSTART) != 0u)
+                    pc_hdr |= pc_blocks == 0u;
             }
             /* symbols */
             WAVE_SYNC();
@@ -814,7 +908,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                         break;
                     if (pos >= cap)
                         INF_ON_FULL;
-                    if constexpr ((SEC & INF_SEC_COUNT) == 0u) {
+                    if constexpr ((SEC & INF_SEC_SYM16) != 0u) {
+                        ON_GLANE0 { pc_ring[pos & (INF_WIN - 1u)] = (uint16_t)sym; }
+                        WAVE_SYNC();
+                    } else if constexpr ((SEC & INF_SEC_COUNT) == 0u) {
                         ON_GLANE0
                         {
                             lds->stage[pos & (INF_STAGE - 1)] = (uint8_t)sym;
@@ -844,7 +941,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                 xb = dsu < 4 ? 0u : (dsu >> 1) - 1u;
                 const uint32_t dist = (dsu < 4 ? dsu : (2u + (dsu & 1u)) << ((dsu >> 1) - 1u)) + 1u +
                                       ((uint32_t)br.hold & ((1u << xb) - 1u));
-                if ((dsu > 29u) | (br.bits < xb) | (dist > dmax) | (pos >= cap) | (dist > pos - out_base)) {
+                if ((dsu > 29u) | (br.bits < xb) | (dist > dmax) | (pos >= cap) | (!PIECE_OUT && dist > pos - out_base)) {
                     if (dsu > 29u)
                         INF_BAD;
                     if (br.bits < xb)
@@ -861,6 +958,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                 INF_TAKE(ex, xb);
                 if constexpr (SEC != 0u)
                     sec_maxd = dist > sec_maxd ? dist : sec_maxd;
+                if constexpr (PIECE_OUT) {
+                    if (dist > pos && dist - pos > pc_reach)
+                        pc_reach = dist - pos;
+                }
                 uint32_t can = len;
                 if (can > cap - pos)
                     can = cap - pos;
@@ -870,6 +971,41 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                  * far more than the error of the reciprocal -- a handful of instructions where the
                  * integer division is ~30 */
                 const float rdist = RCP_F32((float)dist);
+                if constexpr ((SEC & INF_SEC_SYM16) != 0u) {
+                    /* (a read never meets this copy's own writes: it lies before pos, and the slot of
+                     * a write is read, if at all, by the same or a lower lane) */
+                    for (uint32_t k = 0; k < can; k += GRP) {
+                        FOR_GLANES
+                        {
+                            uint32_t i = k + (uint32_t)GLANE;
+                            if (i < can) {
+                                const uint32_t q = (uint32_t)(((float)i + 0.5f) * rdist);
+                                const uint32_t s = pos - dist + (i - q * dist);
+                                const uint16_t v = (int32_t)s < 0 ? (uint16_t)(INF_PH | (INF_WIN + s))
+                                                                  : pc_ring[s & (INF_WIN - 1u)];
+                                pc_ring[(pos + i) & (INF_WIN - 1u)] = v;
+                            }
+                        }
+                        WAVE_SYNC();
+                    }
+                } else if constexpr ((SEC & INF_SEC_EXTWIN) != 0u) {
+                    for (uint32_t k = 0; k < can; k += GRP) {
+                        FOR_GLANES
+                        {
+                            uint32_t i = k + (uint32_t)GLANE;
+                            if (i < can) {
+                                const uint32_t q = (uint32_t)(((float)i + 0.5f) * rdist);
+                                const uint32_t s = pos - dist + (i - q * dist);
+                                const uint8_t b = (int32_t)s < 0 ? pc_win[INF_WIN + s]
+                                                  : s + INF_STAGE >= pos + can ? lds->stage[s & (INF_STAGE - 1)]
+                                                                               : dst[s];
+                                lds->stage[(pos + i) & (INF_STAGE - 1)] = b;
+                                dst[pos + i] = b;
+                            }
+                        }
+                        WAVE_SYNC();
+                    }
+                } else
                 if constexpr ((SEC & INF_SEC_COUNT) == 0u)
                 for (uint32_t k = 0; k < can; k += GRP) {
                     FOR_GLANES
@@ -922,6 +1058,24 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
         }
         if (last)
             break;
+        if constexpr ((SEC & INF_SEC_BITSTART) != 0u) {
+            /* a block boundary: the end of the piece if a later chunk has it as a candidate */
+            pc_blocks++;
+            const uint64_t b = pc_base + BR_USED;
+            const uint32_t m = (uint32_t)(b / pc_cbits);
+            if (m > pc_chunk && m < pc_nch) {
+                uint32_t hit = 0xffffffffu;
+                for (uint32_t c = 0; c < INF_PC_CANDS; c++)
+                    if (pc->cand[(uint64_t)m * INF_PC_CANDS + c] == b && hit == 0xffffffffu)
+                        hit = c;
+                if (hit != 0xffffffffu) {
+                    pc_link = m * INF_PC_CANDS + hit;
+                    sec_sync = 1;
+                    rc = INF_END;
+                    goto done;
+                }
+            }
+        }
     }
 
     /* CHECK / LENGTH, reference src/inflate.c:1322-1354 */
@@ -961,6 +1115,12 @@ bad:
     if constexpr (SEC != 0u) {
         ON_GLANE0
         {
+            if constexpr ((SEC & INF_SEC_BITSTART) != 0u) {
+                pc->link = 0xffffffffu;
+                pc->reach = pc_reach;
+                pc->hdr_ok = pc_hdr;
+                pc->end_bit = pc_base + BR_USED;
+            }
             si->outcome = sec_hist ? INF_SEC_HISTORY : INF_SEC_ERROR;
             si->stop = (uint32_t)((BR_USED + 7u) >> 3);
             si->out_len = pos;
@@ -990,6 +1150,12 @@ done:
     if constexpr (SEC != 0u) {
         ON_GLANE0
         {
+            if constexpr ((SEC & INF_SEC_BITSTART) != 0u) {
+                pc->link = pc_link;
+                pc->reach = pc_reach;
+                pc->hdr_ok = pc_hdr;
+                pc->end_bit = pc_base + BR_USED;
+            }
             uint32_t used_bytes = (uint32_t)((BR_USED + 7u) >> 3);
             if (exhausted || used_bytes > n)
                 used_bytes = n;

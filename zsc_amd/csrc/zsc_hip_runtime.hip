@@ -26,6 +26,7 @@
 #include "huff_plan.h"
 #include "inflate.h"
 #include "inflate_sections.h"
+#include "inflate_chunks.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "match_table.h"
@@ -673,6 +674,86 @@ __global__ __launch_bounds__(64) void k_sec_finish(const uint8_t *__restrict__ s
     const uint32_t na = *P.q;
     for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
         sec_finish(P, src, res, resume, a);
+}
+
+/* kernel 7 (inflate_chunks.h): any stream inflated in parallel from block starts found by trial, in
+ * six launches ahead of k_sec_finish and k_inflate */
+__global__ __launch_bounds__(64) void k_chk_setup(IchkPlan P)
+{
+    for (uint32_t a = blockIdx.x; a < P.nactive; a += gridDim.x)
+        chk_setup(P, a);
+}
+
+__global__ __launch_bounds__(64) void k_chk_scan(const uint8_t *__restrict__ src, IchkPlan P)
+{
+    for (uint32_t t = blockIdx.x; t < P.sp.ntiles; t += gridDim.x)
+        chk_scan(P, src, t);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_chk_count(
+    const uint8_t *__restrict__ src, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    chk_count_worker<false>(P, src, &lds_all[grp], &info[grp], &piece[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_chk_want(IchkPlan P)
+{
+    for (uint32_t a = blockIdx.x; a < P.nactive; a += gridDim.x)
+        chk_want(P, a);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_chk_retry(
+    const uint8_t *__restrict__ src, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    chk_count_worker<true>(P, src, &lds_all[grp], &info[grp], &piece[grp]);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_chk_resolve(
+    const uint8_t *__restrict__ src, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + grp; a < P.nactive; a += gridDim.x * INF_PER_WAVE)
+        chk_resolve(P, src, &lds_all[grp], &info[grp], &piece[grp], a);
+}
+
+#define CHK_WINDOW_THREADS 1024
+__global__ __launch_bounds__(CHK_WINDOW_THREADS) void k_chk_window(IchkPlan P)
+{
+    for (uint32_t a = blockIdx.x; a < P.nactive; a += gridDim.x)
+        chk_windows(P, P.sp.active[a], threadIdx.x, CHK_WINDOW_THREADS, [] { __syncthreads(); });
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_chk_write(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    chk_write_worker(P, src, dst, &lds_all[grp], &info[grp], &piece[grp]);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -2358,6 +2439,10 @@ struct zsc_hip_inflate_plan {
     uint64_t ncand_total = 0, scratch_bytes = 0;
     DevBuf d_sitems, d_tiles, d_tile_cnt, d_tile_off, d_scount, d_nsec, d_sst, d_active, d_q;
     DevBuf d_cstart, d_cstop, d_clink, d_clen, d_chain_k, d_chain_off, d_chain_ck;
+    /* chunks plans only (inflate_chunks.h; they also use the sections plan's buffers above) */
+    bool chunks = false;
+    IchkPlan cp = {};
+    DevBuf d_cand, d_cused, d_creach, d_want, d_ring, d_win;
     const void *last_src = nullptr;
     void *last_dst = nullptr;
     hipStream_t last_stream = nullptr;
@@ -2451,7 +2536,8 @@ static void inflate_plan_release(zsc_hip_inflate_plan *pl)
     for (DevBuf *b : {&pl->d_items, &pl->d_order, &pl->d_res, &pl->d_resume, &pl->d_pending, &pl->d_sitems,
                       &pl->d_tiles, &pl->d_tile_cnt, &pl->d_tile_off, &pl->d_scount, &pl->d_nsec, &pl->d_sst,
                       &pl->d_active, &pl->d_q, &pl->d_cstart, &pl->d_cstop, &pl->d_clink, &pl->d_clen,
-                      &pl->d_chain_k, &pl->d_chain_off, &pl->d_chain_ck})
+                      &pl->d_chain_k, &pl->d_chain_off, &pl->d_chain_ck, &pl->d_cand, &pl->d_cused, &pl->d_creach,
+                      &pl->d_want, &pl->d_ring, &pl->d_win})
         b->release();
 }
 
@@ -2538,6 +2624,125 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan 
     return Z_OK;
 }
 
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_chunks(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                         const U32 *source_lens, const uint64_t *src_offsets,
+                                                         const U32 *dest_caps, const uint64_t *dst_offsets,
+                                                         I32 window_bits, U32 chunk_bytes)
+{
+    ZlibReturn rc = zsc_hip_inflate_plan_create(plan_out, count, source_lens, src_offsets, dest_caps, dst_offsets,
+                                                window_bits);
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    zsc_hip_inflate_plan *pl = *plan_out;
+    pl->chunks = true;
+    const uint32_t cb = chunk_bytes == 0 ? CHK_DEFAULT_BYTES : std::max<uint32_t>(chunk_bytes, CHK_MIN_BYTES);
+    /* per stream longer than a chunk (and with less than 2 GiB of output: positions inside a piece
+     * are signed 32-bit): its chunks; the scan visits every chunk but the first */
+    std::vector<IsecItem> items(count);
+    std::vector<IsecTile> scan;
+    std::vector<uint32_t> active;
+    uint64_t nchunks = 0;
+    for (U32 i = 0; i < count; i++) {
+        IsecItem &it = items[i];
+        it.src_off = src_offsets[i];
+        it.dst_off = dst_offsets[i];
+        it.src_len = source_lens[i];
+        it.dst_cap = dest_caps[i];
+        it.cap = 0;
+        it.tile0 = (uint32_t)nchunks;
+        it.ntiles = 0;
+        it.pad = 0;
+        if (source_lens[i] > cb && dest_caps[i] < 0x80000000u) {
+            it.ntiles = (uint32_t)(((uint64_t)source_lens[i] + cb - 1u) / cb);
+            for (uint32_t k = 1; k < it.ntiles; k++)
+                scan.push_back(IsecTile{i, k});
+            active.push_back(i);
+            nchunks += it.ntiles;
+        }
+    }
+    if (nchunks >= 0x03ffffffull) { /* (links hold chunk * 4 + candidate in 28 bits) */
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    const uint64_t nt = std::max<uint64_t>(1, scan.size()), nc = std::max<uint64_t>(1, count);
+    const uint64_t ch = std::max<uint64_t>(1, nchunks);
+    bool ok = pl->d_sitems.ensure(sizeof(IsecItem) * nc) && pl->d_tiles.ensure(sizeof(IsecTile) * nt) &&
+              pl->d_nsec.ensure(4 * nc) && pl->d_sst.ensure(sizeof(IsecStream) * nc) && pl->d_active.ensure(4 * nc) &&
+              pl->d_q.ensure(16) && pl->d_cstop.ensure(4 * ch) && pl->d_clink.ensure(4 * ch) &&
+              pl->d_clen.ensure(4 * ch) && pl->d_chain_k.ensure(4 * ch) && pl->d_chain_off.ensure(4 * ch) &&
+              pl->d_chain_ck.ensure(4 * ch) && pl->d_cand.ensure(8ull * INF_PC_CANDS * ch) &&
+              pl->d_cused.ensure(4 * ch) && pl->d_creach.ensure(4 * ch) && pl->d_want.ensure(4 * ch) && pl->d_ring.ensure(2ull * INF_WIN * ch) &&
+              pl->d_win.ensure((uint64_t)INF_WIN * ch);
+    if (ok && count)
+        ok = hipMemcpy(pl->d_sitems.p, items.data(), sizeof(IsecItem) * count, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !scan.empty())
+        ok = hipMemcpy(pl->d_tiles.p, scan.data(), sizeof(IsecTile) * scan.size(), hipMemcpyHostToDevice) ==
+             hipSuccess;
+    if (ok && !active.empty())
+        ok = hipMemcpy(pl->d_active.p, active.data(), 4 * active.size(), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    IchkPlan &P = pl->cp;
+    P.sp.items = (const IsecItem *)pl->d_sitems.p;
+    P.sp.tiles = (const IsecTile *)pl->d_tiles.p;
+    P.sp.nsec = (uint32_t *)pl->d_nsec.p;
+    P.sp.st = (IsecStream *)pl->d_sst.p;
+    P.sp.active = (uint32_t *)pl->d_active.p;
+    P.sp.q = (uint32_t *)pl->d_q.p;
+    P.sp.cstop = (uint32_t *)pl->d_cstop.p;
+    P.sp.clink = (uint32_t *)pl->d_clink.p;
+    P.sp.clen = (uint32_t *)pl->d_clen.p;
+    P.sp.chain_k = (uint32_t *)pl->d_chain_k.p;
+    P.sp.chain_off = (uint32_t *)pl->d_chain_off.p;
+    P.sp.chain_ck = (uint32_t *)pl->d_chain_ck.p;
+    P.sp.count = count;
+    P.sp.ntiles = (uint32_t)scan.size();
+    P.sp.pool = (uint32_t)nchunks;
+    P.sp.window_bits = window_bits;
+    P.sp.work_mul = SEC_WORK_MUL;
+    P.sp.work_add = SEC_WORK_ADD;
+    P.cand = (uint64_t *)pl->d_cand.p;
+    P.cused = (uint32_t *)pl->d_cused.p;
+    P.creach = (uint32_t *)pl->d_creach.p;
+    P.want = (uint32_t *)pl->d_want.p;
+    P.ring = (uint16_t *)pl->d_ring.p;
+    P.win = (uint8_t *)pl->d_win.p;
+    P.nactive = (uint32_t)active.size();
+    P.chunk_bytes = cb;
+    pl->ncand_total = nchunks;
+    pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
+                        (8ull * INF_PC_CANDS + 36 + 3ull * INF_WIN) * ch;
+    return Z_OK;
+}
+
+/* the launches of a chunks plan, ahead of k_inflate (none when no stream is longer than a chunk) */
+static void chk_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
+{
+    const IchkPlan &P = pl->cp;
+    if (P.nactive == 0)
+        return;
+    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
+    const uint32_t per_stream = std::max(1u, std::min(P.nactive, fill));
+    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
+    const uint32_t scans = std::max(1u, std::min(P.sp.ntiles, fill * 4u));
+    hipLaunchKernelGGL(k_chk_setup, dim3(per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_chk_scan, dim3(scans), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_chk_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_chk_want, dim3(per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_chk_retry, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_chk_resolve, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
+                       (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_chk_window, dim3(std::min<uint32_t>(P.nactive, (uint32_t)g_cus * 4u)), dim3(CHK_WINDOW_THREADS), 0, st, P);
+    hipLaunchKernelGGL(k_chk_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P);
+    hipLaunchKernelGGL(k_sec_finish, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
+                       (const uint8_t *)d_src, P.sp, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+}
+
 /* the six launches of a sections plan, ahead of k_inflate */
 static void sec_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
 {
@@ -2575,9 +2780,15 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
         HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
     }
+    if (pl->chunks) {
+        HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+        HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
+    }
     (void)hipEventRecord(pl->ev0, st);
     if (pl->sections)
         sec_enqueue(pl, d_src, d_dst, st);
+    if (pl->chunks)
+        chk_enqueue(pl, d_src, d_dst, st);
     hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, st, (const uint8_t *)d_src,
                        (uint8_t *)d_dst, (const ZdInfItem *)pl->d_items.p,
                        (const uint32_t *)pl->d_order.p, (InfResult *)pl->d_res.p,
@@ -2653,7 +2864,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U3
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     ZSC_ASSERT(sections != Z_NULL);
-    if (!pl->sections || !pl->last_dst || pl->count == 0) {
+    if (!(pl->sections || pl->chunks) || !pl->last_dst || pl->count == 0) {
         for (uint32_t i = 0; i < pl->count; i++)
             sections[i] = 0;
         return Z_OK;
@@ -2669,25 +2880,32 @@ extern "C" uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_pla
 }
 
 static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
-                                        U32 *dest_lens, I32 *statuses, I32 window_bits, bool sections);
+                                        U32 *dest_lens, I32 *statuses, I32 window_bits, int kind);
 
 /* host-pointer batch: stage through one pair of device buffers */
 extern "C" ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources,
                                                U32 *source_lens, U8 *const *dests,
                                                U32 *dest_lens, I32 *statuses, I32 window_bits)
 {
-    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, false);
+    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 0);
 }
 
 extern "C" ZlibReturn zsc_hip_uncompress_sections_batch(U32 count, const U8 *const *sources,
                                                         U32 *source_lens, U8 *const *dests,
                                                         U32 *dest_lens, I32 *statuses, I32 window_bits)
 {
-    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, true);
+    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 1);
+}
+
+extern "C" ZlibReturn zsc_hip_uncompress_chunks_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                                      U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                                      I32 window_bits)
+{
+    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 2);
 }
 
 static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
-                                        U32 *dest_lens, I32 *statuses, I32 window_bits, bool sections)
+                                        U32 *dest_lens, I32 *statuses, I32 window_bits, int kind)
 {
     DeviceScope scope;
     ZSC_ASSERT(sources != Z_NULL);
@@ -2707,10 +2925,12 @@ static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32
         db += ((uint64_t)dest_lens[i] + 64u + 15u) & ~15ull;
     }
     zsc_hip_inflate_plan *pl = nullptr;
-    ZlibReturn rc = sections ? zsc_hip_inflate_plan_create_sections(&pl, count, source_lens, so.data(), dest_lens,
-                                                                    dof.data(), window_bits)
-                             : zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_lens,
-                                                           dof.data(), window_bits);
+    ZlibReturn rc = kind == 1 ? zsc_hip_inflate_plan_create_sections(&pl, count, source_lens, so.data(), dest_lens,
+                                                                     dof.data(), window_bits)
+                    : kind == 2 ? zsc_hip_inflate_plan_create_chunks(&pl, count, source_lens, so.data(), dest_lens,
+                                                                     dof.data(), window_bits, 0)
+                                : zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_lens,
+                                                              dof.data(), window_bits);
     if (rc != Z_OK)
         return rc;
     DevBuf d_src, d_dst;
