@@ -236,6 +236,34 @@ ZlibReturn zsc_hip_uncompress_chunks_batch(U32 count, const U8 *const *sources, 
                                            U8 *const *dests, U32 *dest_lens, I32 *statuses,
                                            I32 window_bits);
 
+/* Resync plans: the same arguments as zsc_hip_inflate_plan_create_sections; a sections plan that also
+ * finishes damaged streams in parallel.  Where a section ends in a data error, the run does what
+ * zsc_uncompress does (inflateSync): it looks for the next 00 00 FF FF -- in what the bit buffer held,
+ * then in the input -- and goes on decoding behind it, so the stream ends with Z_DATA_ERROR, the
+ * output salvaged, the reference's consumed count and its number of data errors
+ * (zsc_amd/csrc/inflate_resync.h).  Every stream the path cannot finish that way is decoded serially
+ * from its start: everything a sections plan sends there except the data errors and their
+ * resynchronisation, and besides an error in the zlib / gzip header, a data error where the output has
+ * reached dest_caps[i], a resynchronisation that lands where no section was decoded, a distance beyond the
+ * output of a section entered at a marker, a pattern inside or behind a failing trailer, and more data
+ * errors than the reference's loop allows (max(dest_caps[i], 10) inflate() calls).  So status, output
+ * bytes and consumed equal the plain plan's for every input.  _run, _results, _destroy,
+ * zsc_hip_inflate_plan_sections (chain entries decoded in parallel, a damaged section's partial one
+ * included; 0 for serial) and zsc_hip_inflate_plan_scratch_bytes work on it.  Scratch: a sections
+ * plan's, plus 12 bytes per candidate pool slot and 16 bytes per stream. */
+ZlibReturn zsc_hip_inflate_plan_create_resync(zsc_hip_inflate_plan **plan, U32 count,
+                                              const U32 *source_lens, const uint64_t *src_offsets,
+                                              const U32 *dest_caps, const uint64_t *dst_offsets,
+                                              I32 window_bits);
+/* zsc_hip_uncompress_batch through a resync plan: the same signature and per-item semantics */
+ZlibReturn zsc_hip_uncompress_resync_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                           U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                           I32 window_bits);
+/* after _results, for every plan kind: per stream, the data errors the reference's zsc_uncompress loop
+ * counts (one per inflate() call that returned Z_DATA_ERROR; it only warns of them).  0 for a stream
+ * that decoded cleanly. */
+ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *plan, U32 *errors);
+
 #ifdef __cplusplus
 }
 #endif

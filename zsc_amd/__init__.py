@@ -9,6 +9,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
 * :func:`uncompress_sections_batch` -- the full-flush sections of each stream inflated in parallel;
 * :func:`uncompress_chunks_batch` -- any long stream inflated in parallel pieces from block starts
   found by trial;
+* :func:`uncompress_resync_batch` -- full-flush sections inflated in parallel, damaged streams
+  resynchronised at the next flush marker as zsc_uncompress does;
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -21,6 +23,6 @@ from .api import (  # noqa: F401
     uncompress_get_min_work_buf_size,
     compress, compress2, compress_gzip, uncompress, uncompress2, uncompress_gzip,
     compress_batch, compress_sections_batch, compress_sections_device, uncompress_batch, uncompress_sections_batch,
-    uncompress_chunks_batch, DeflatePlan, InflatePlan,
+    uncompress_chunks_batch, uncompress_resync_batch, DeflatePlan, InflatePlan,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

@@ -84,6 +84,9 @@ def _load() -> C.CDLL:
     L.zsc_hip_inflate_plan_create_chunks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p, u64p,
                                                      C.c_int32, C.c_uint32]
     L.zsc_hip_uncompress_chunks_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes
+    L.zsc_hip_inflate_plan_create_resync.argtypes = L.zsc_hip_inflate_plan_create_sections.argtypes
+    L.zsc_hip_uncompress_resync_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes
+    L.zsc_hip_inflate_plan_data_errors.argtypes = [C.c_void_p, u32p]
     L.zsc_hip_inflate_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.zsc_hip_inflate_plan_results.argtypes = [C.c_void_p, u32p, u32p, i32p, C.POINTER(C.c_float)]
     L.zsc_hip_inflate_plan_destroy.argtypes = [C.c_void_p]
@@ -342,6 +345,14 @@ def uncompress_chunks_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
     return _uncompress_batch(lib.zsc_hip_uncompress_chunks_batch, sources, dest_caps, window_bits)
 
 
+def uncompress_resync_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
+                            window_bits: int = DEF_WBITS):
+    """zsc_hip_uncompress_resync_batch: as uncompress_batch, with the full-flush sections of each
+    stream decoded in parallel, damaged streams included: a data error resynchronises at the next
+    flush marker as zsc_uncompress does (results identical to uncompress_batch for every input)."""
+    return _uncompress_batch(lib.zsc_hip_uncompress_resync_batch, sources, dest_caps, window_bits)
+
+
 def _uncompress_batch(fn, sources, dest_caps, window_bits):
     count = len(sources)
     srcs = (C.c_char_p * count)(*sources)
@@ -360,11 +371,13 @@ class InflatePlan:
     (zsc_hip_inflate_plan_create_sections: full-flush sections decoded in parallel; it takes no
     decode_order).  chunks=True makes a chunks plan (zsc_hip_inflate_plan_create_chunks: any stream longer
     than chunk_bytes decoded in parallel pieces; chunk_bytes 0 = the library's default; no decode_order
-    either)."""
+    either).  resync=True makes a resync plan (zsc_hip_inflate_plan_create_resync: a sections plan that
+    also decodes damaged streams in parallel, resynchronising at the next flush marker after a data
+    error); it implies sections."""
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int],
                  window_bits: int = DEF_WBITS, decode_order: Sequence[int] | None = None,
-                 sections: bool = False, chunks: bool = False, chunk_bytes: int = 0):
+                 sections: bool = False, chunks: bool = False, chunk_bytes: int = 0, resync: bool = False):
         self.count = n = len(source_lens)
         so, do, sb, db = [], [], 0, 0
         for sl, dc in zip(source_lens, dest_caps):
@@ -375,6 +388,8 @@ class InflatePlan:
         self.src_offsets, self.dst_offsets = so, do
         self.src_bytes, self.dst_bytes = sb + 64, db + 64
         self._h = C.c_void_p()
+        if resync and chunks:
+            raise ValueError("a resync plan is a sections plan, not a chunks plan")
         if sections and chunks:
             raise ValueError("a plan is a sections plan or a chunks plan, not both")
         if chunks:
@@ -383,10 +398,11 @@ class InflatePlan:
             rc = lib.zsc_hip_inflate_plan_create_chunks(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
                                                         (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
                                                         (C.c_uint64 * n)(*do), window_bits, chunk_bytes)
-        elif sections:
+        elif sections or resync:
             if decode_order is not None:
                 raise ValueError("a sections plan takes no decode_order")
-            rc = lib.zsc_hip_inflate_plan_create_sections(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
+            create = lib.zsc_hip_inflate_plan_create_resync if resync else lib.zsc_hip_inflate_plan_create_sections
+            rc = create(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
                                                           (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
                                                           (C.c_uint64 * n)(*do), window_bits)
         else:
@@ -421,8 +437,18 @@ class InflatePlan:
             raise RuntimeError(f"zsc_hip_inflate_plan_sections failed: {rc}")
         return list(out)[:n]
 
+    def data_errors(self) -> List[int]:
+        """After results(), for every plan kind: per stream, the data errors zsc_uncompress's loop counts
+        (0 for a stream that decoded cleanly)."""
+        n = self.count
+        out = (C.c_uint32 * max(n, 1))()
+        rc = lib.zsc_hip_inflate_plan_data_errors(self._h, out)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_data_errors failed: {rc}")
+        return list(out)[:n]
+
     def scratch_bytes(self) -> int:
-        """Device scratch of a sections or chunks plan beyond a plain plan's (0 for a plain plan)."""
+        """Device scratch of a sections, chunks or resync plan beyond a plain plan's (0 for a plain plan)."""
         return int(lib.zsc_hip_inflate_plan_scratch_bytes(self._h))
 
     def close(self) -> None:

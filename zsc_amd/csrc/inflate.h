@@ -226,8 +226,10 @@ DEV int inf_build(CT *c, const uint8_t *lens, int n, int kind)
  * from bit sy_start, after its "hold <<= bits & 7") followed by the input from byte nin on.
  * Returns the number of input bytes up to the end of the pattern, or 0xffffffff when there
  * is none. */
-DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, uint32_t sy_rb,
-                                      uint32_t nin)
+/* the bytes inflateSync searches first: what the reference's bit buffer holds at the error, sy_rb bits
+ * of the stream from bit sy_start, after its "hold <<= bits & 7" (:1571); the low sy_rb / 8 bytes
+ * count (inflate_resync.h shares this) */
+DEV uint32_t inf_sync_hold(const uint8_t *src, uint32_t n, uint64_t sy_start, uint32_t sy_rb)
 {
     uint32_t hold = 0;
     for (uint32_t k = 0; k < sy_rb; k += 8u) {
@@ -240,10 +242,14 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
     }
     if (sy_rb < 32u)
         hold &= (1u << sy_rb) - 1u;
-    uint32_t rb = sy_rb;
-    hold <<= rb & 7u; /* sic, :1571 */
-    rb -= rb & 7u;
-    const uint32_t nh = rb >> 3; /* bytes of hold searched before the input */
+    return hold << (sy_rb & 7u); /* sic, :1571 */
+}
+
+DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, uint32_t sy_rb,
+                                      uint32_t nin)
+{
+    const uint32_t hold = inf_sync_hold(src, n, sy_start, sy_rb);
+    const uint32_t nh = sy_rb >> 3; /* bytes of hold searched before the input */
     const uint32_t vlen = nh + (n - nin);
     for (uint32_t base = 0; base + 4u <= vlen; base += GRP) {
         LANEVAR(int, _hit);
@@ -286,6 +292,9 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
 #define INF_SEC_BITSTART 8u
 #define INF_SEC_SYM16 16u
 #define INF_SEC_EXTWIN 32u
+/* resync variants (inflate_resync.h), with si pointing to an InfSecErr:
+ *   INF_SEC_ERRSTATE record the error state inflateSync would start from (InfSecErr) */
+#define INF_SEC_ERRSTATE 64u
 #define INF_WIN 32768u   /* window entries: win[INF_WIN - d] is the byte d before the piece */
 #define INF_PH 0x8000u   /* a placeholder symbol of the 16-bit output */
 #define INF_PC_CANDS 4u  /* candidates per chunk */
@@ -303,6 +312,16 @@ typedef struct {
     uint32_t dmax;    /* the distance limit the header set */
     uint32_t gzip;    /* the header was a gzip header */
 } InfSecInfo;
+
+/* INF_SEC_ERRSTATE: the section's way out, and at a data error what the reference's bit buffer held */
+#define INF_SEC_ERR_NONE 0u /* no data error: the outcome says how it ended */
+#define INF_SEC_ERR_HEAD 1u /* a data error in the zlib / gzip header */
+#define INF_SEC_ERR_BODY 2u /* a data error in the blocks */
+struct InfSecErr : InfSecInfo {
+    uint32_t err;      /* INF_SEC_ERR_* */
+    uint32_t sy_rb;    /* bits in the reference's hold at the error */
+    uint64_t sy_start; /* where they start: bit offset from job.src */
+};
 
 typedef struct {
     /* in */
@@ -396,6 +415,8 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     (void)pc_blocks;
     (void)pc_ring;
     (void)pc_win;
+    uint32_t sec_body = 0; /* (resync variants only) the header is behind: a data error is one in the blocks */
+    (void)sec_body;
 
 /* top up the bit buffer to at least 32 bits (or to the end of the input) */
 #define INF_REFILL()                                                                          \
@@ -690,6 +711,9 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
             (void)t;
         }
     }
+
+    if constexpr ((SEC & INF_SEC_ERRSTATE) != 0u)
+        sec_body = 1;
 
     /* blocks */
     for (;;) {
@@ -1127,6 +1151,12 @@ bad:
             si->maxd = sec_maxd;
             si->dmax = dmax;
             si->gzip = (uint32_t)gzip;
+            if constexpr ((SEC & INF_SEC_ERRSTATE) != 0u) {
+                InfSecErr *se = static_cast<InfSecErr *>(si);
+                se->err = sec_body ? INF_SEC_ERR_BODY : INF_SEC_ERR_HEAD;
+                se->sy_rb = sy_rb;
+                se->sy_start = sy_start;
+            }
         }
         WAVE_SYNC();
         return 0;
@@ -1165,6 +1195,8 @@ done:
             si->maxd = sec_maxd;
             si->dmax = dmax;
             si->gzip = (uint32_t)gzip;
+            if constexpr ((SEC & INF_SEC_ERRSTATE) != 0u)
+                static_cast<InfSecErr *>(si)->err = INF_SEC_ERR_NONE;
         }
         WAVE_SYNC();
         return 0;

@@ -444,6 +444,34 @@ DEV void sec_write_worker(const IsecPlan &P, const uint8_t *src_all, uint8_t *ds
     }
 }
 
+/* the check value of a stream's output from its chain's slices (chain_ck, clen): lane l combines the
+ * slices of its share of the chain, then the lanes' results are combined in order */
+DEV uint32_t sec_chain_check(const IsecPlan &P, uint32_t cb, uint32_t nchain, uint32_t gzip)
+{
+    const uint32_t per = (nchain + GRP - 1u) / GRP;
+    LANEVAR(uint32_t, pc);
+    LANEVAR(uint32_t, pl);
+    FOR_GLANES
+    {
+        const uint32_t j0 = (uint32_t)GLANE * per;
+        const uint32_t j1 = j0 + per < nchain ? j0 + per : nchain;
+        uint32_t c = gzip ? 0u : 1u, l = 0;
+        for (uint32_t j = j0; j < j1; j++) {
+            const uint32_t len = P.clen[cb + P.chain_k[cb + j]], cj = P.chain_ck[cb + j];
+            c = gzip ? sec_crc32_combine(c, cj, len) : sec_adler32_combine(c, cj, len);
+            l += len;
+        }
+        LV(pc) = c;
+        LV(pl) = l;
+    }
+    uint32_t want = gzip ? 0u : 1u;
+    for (uint32_t l = 0; l < GRP; l++) {
+        const uint32_t c = GREADLANE(pc, l), len = GREADLANE(pl, l);
+        want = gzip ? sec_crc32_combine(want, c, len) : sec_adler32_combine(want, c, len);
+    }
+    return want;
+}
+
 /* step 6 for the a-th active stream: combine, check the trailer, finish */
 DEV void sec_finish(const IsecPlan &P, const uint8_t *src_all, InfResult *res, InfResume *resume, uint32_t a)
 {
@@ -468,28 +496,7 @@ DEV void sec_finish(const IsecPlan &P, const uint8_t *src_all, InfResult *res, I
             return; /* truncated trailer: Z_BUF_ERROR, the serial decoder says so */
         const uint32_t v = inf_input_dword(src, t, n);
         if (wrap & 4) {
-            /* lane l combines the slices of its share of the chain, then lane 0 the lanes' results */
-            const uint32_t per = (nchain + GRP - 1u) / GRP;
-            LANEVAR(uint32_t, pc);
-            LANEVAR(uint32_t, pl);
-            FOR_GLANES
-            {
-                const uint32_t j0 = (uint32_t)GLANE * per;
-                const uint32_t j1 = j0 + per < nchain ? j0 + per : nchain;
-                uint32_t c = gzip ? 0u : 1u, l = 0;
-                for (uint32_t j = j0; j < j1; j++) {
-                    const uint32_t len = P.clen[cb + P.chain_k[cb + j]], cj = P.chain_ck[cb + j];
-                    c = gzip ? sec_crc32_combine(c, cj, len) : sec_adler32_combine(c, cj, len);
-                    l += len;
-                }
-                LV(pc) = c;
-                LV(pl) = l;
-            }
-            uint32_t want = gzip ? 0u : 1u;
-            for (uint32_t l = 0; l < GRP; l++) {
-                const uint32_t c = GREADLANE(pc, l), len = GREADLANE(pl, l);
-                want = gzip ? sec_crc32_combine(want, c, len) : sec_adler32_combine(want, c, len);
-            }
+            const uint32_t want = sec_chain_check(P, cb, nchain, gzip);
             const uint32_t got = gzip ? v : ((v >> 24) | ((v >> 8) & 0xff00u) | ((v & 0xff00u) << 8) | (v << 24));
             if (got != want)
                 return;

@@ -27,6 +27,7 @@
 #include "inflate.h"
 #include "inflate_sections.h"
 #include "inflate_chunks.h"
+#include "inflate_resync.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "match_table.h"
@@ -754,6 +755,47 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU
     if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
         lds_all[grp].cktab = crc_table;
     chk_write_worker(P, src, dst, &lds_all[grp], &info[grp], &piece[grp]);
+}
+
+/* kernel 8 (inflate_resync.h): damaged full-flush streams inflated in parallel, with inflateSync's
+ * resynchronisation; k_sec_scan and k_sec_setup, then these four, ahead of k_inflate */
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_rsy_count(
+    const uint8_t *__restrict__ src, IrsyPlan R)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecErr info[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    rsy_count_worker(R, src, &lds_all[grp], &info[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_rsy_resolve(const uint8_t *__restrict__ src, IrsyPlan R)
+{
+    const uint32_t na = *R.sp.q;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
+        rsy_resolve(R, src, a);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_rsy_write(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, IrsyPlan R)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    rsy_write_worker(R, src, dst, &lds_all[grp], &info[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_rsy_finish(const uint8_t *__restrict__ src, IrsyPlan R,
+                                                   InfResult *__restrict__ res, InfResume *__restrict__ resume)
+{
+    const uint32_t na = *R.sp.q;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
+        rsy_finish(R, src, res, resume, a);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -2443,6 +2485,10 @@ struct zsc_hip_inflate_plan {
     bool chunks = false;
     IchkPlan cp = {};
     DevBuf d_cand, d_cused, d_creach, d_want, d_ring, d_win;
+    /* resync plans only (inflate_resync.h; sections plans with these buffers besides) */
+    bool resync = false;
+    IrsyPlan rp = {};
+    DevBuf d_cerr, d_chain_fl, d_rst;
     const void *last_src = nullptr;
     void *last_dst = nullptr;
     hipStream_t last_stream = nullptr;
@@ -2537,7 +2583,7 @@ static void inflate_plan_release(zsc_hip_inflate_plan *pl)
                       &pl->d_tiles, &pl->d_tile_cnt, &pl->d_tile_off, &pl->d_scount, &pl->d_nsec, &pl->d_sst,
                       &pl->d_active, &pl->d_q, &pl->d_cstart, &pl->d_cstop, &pl->d_clink, &pl->d_clen,
                       &pl->d_chain_k, &pl->d_chain_off, &pl->d_chain_ck, &pl->d_cand, &pl->d_cused, &pl->d_creach,
-                      &pl->d_want, &pl->d_ring, &pl->d_win})
+                      &pl->d_want, &pl->d_ring, &pl->d_win, &pl->d_cerr, &pl->d_chain_fl, &pl->d_rst})
         b->release();
 }
 
@@ -2720,6 +2766,33 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_chunks(zsc_hip_inflate_plan **
     return Z_OK;
 }
 
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_resync(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                         const U32 *source_lens, const uint64_t *src_offsets,
+                                                         const U32 *dest_caps, const uint64_t *dst_offsets,
+                                                         I32 window_bits)
+{
+    ZlibReturn rc = zsc_hip_inflate_plan_create_sections(plan_out, count, source_lens, src_offsets, dest_caps,
+                                                         dst_offsets, window_bits);
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    zsc_hip_inflate_plan *pl = *plan_out;
+    pl->resync = true;
+    const uint64_t cand = pl->ncand_total, nc = std::max(1u, count);
+    if (!pl->d_cerr.ensure(8 * cand) || !pl->d_chain_fl.ensure(4 * cand) || !pl->d_rst.ensure(sizeof(IrsyStream) * nc)) {
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    IrsyPlan &R = pl->rp;
+    R.sp = pl->sp;
+    R.cerr = (uint64_t *)pl->d_cerr.p;
+    R.chain_fl = (uint32_t *)pl->d_chain_fl.p;
+    R.rst = (IrsyStream *)pl->d_rst.p;
+    pl->scratch_bytes += 12 * cand + sizeof(IrsyStream) * nc;
+    return Z_OK;
+}
+
 /* the launches of a chunks plan, ahead of k_inflate (none when no stream is longer than a chunk) */
 static void chk_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
 {
@@ -2741,6 +2814,26 @@ static void chk_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst
     hipLaunchKernelGGL(k_chk_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P);
     hipLaunchKernelGGL(k_sec_finish, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
                        (const uint8_t *)d_src, P.sp, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+}
+
+/* the launches of a resync plan, ahead of k_inflate: the sections plan's scan and setup, then its own */
+static void rsy_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
+{
+    const IrsyPlan &R = pl->rp;
+    const IsecPlan &P = R.sp;
+    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
+    const uint32_t per_stream = std::max(1u, std::min(pl->count, fill));
+    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
+    const uint32_t tiles = std::max(1u, std::min(P.ntiles, fill * 4u));
+    const uint32_t per_group = (per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE;
+    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 0);
+    hipLaunchKernelGGL(k_sec_setup, dim3(per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 1);
+    hipLaunchKernelGGL(k_rsy_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, R);
+    hipLaunchKernelGGL(k_rsy_resolve, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, R);
+    hipLaunchKernelGGL(k_rsy_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, R);
+    hipLaunchKernelGGL(k_rsy_finish, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, R,
+                       (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
 }
 
 /* the six launches of a sections plan, ahead of k_inflate */
@@ -2785,7 +2878,9 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
     }
     (void)hipEventRecord(pl->ev0, st);
-    if (pl->sections)
+    if (pl->resync)
+        rsy_enqueue(pl, d_src, d_dst, st);
+    else if (pl->sections)
         sec_enqueue(pl, d_src, d_dst, st);
     if (pl->chunks)
         chk_enqueue(pl, d_src, d_dst, st);
@@ -2874,6 +2969,25 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U3
     return Z_OK;
 }
 
+extern "C" ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *pl, U32 *errors)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(errors != Z_NULL);
+    if (!pl->last_dst || pl->count == 0) {
+        for (uint32_t i = 0; i < pl->count; i++)
+            errors[i] = 0;
+        return Z_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+    std::vector<InfResume> rs(pl->count);
+    HIP_TRY(hipMemcpy(rs.data(), pl->d_resume.p, sizeof(InfResume) * pl->count, hipMemcpyDeviceToHost),
+            return Z_STREAM_ERROR);
+    for (uint32_t i = 0; i < pl->count; i++)
+        errors[i] = rs[i].errors;
+    return Z_OK;
+}
+
 extern "C" uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_plan *pl)
 {
     return pl ? pl->scratch_bytes : 0;
@@ -2904,6 +3018,13 @@ extern "C" ZlibReturn zsc_hip_uncompress_chunks_batch(U32 count, const U8 *const
     return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 2);
 }
 
+extern "C" ZlibReturn zsc_hip_uncompress_resync_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                                      U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                                      I32 window_bits)
+{
+    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 3);
+}
+
 static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
                                         U32 *dest_lens, I32 *statuses, I32 window_bits, int kind)
 {
@@ -2929,6 +3050,8 @@ static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32
                                                                      dof.data(), window_bits)
                     : kind == 2 ? zsc_hip_inflate_plan_create_chunks(&pl, count, source_lens, so.data(), dest_lens,
                                                                      dof.data(), window_bits, 0)
+                    : kind == 3 ? zsc_hip_inflate_plan_create_resync(&pl, count, source_lens, so.data(), dest_lens,
+                                                                     dof.data(), window_bits)
                                 : zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_lens,
                                                               dof.data(), window_bits);
     if (rc != Z_OK)
