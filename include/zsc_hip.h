@@ -141,6 +141,10 @@ uint64_t zsc_hip_deflate_plan_scratch_bytes(const zsc_hip_deflate_plan *plan);
 /* number of sub-batches (kernel launch sets) one run of the plan issues */
 U32 zsc_hip_deflate_plan_sub_batches(const zsc_hip_deflate_plan *plan);
 
+/* how the plan's long buffers without joints are parsed at levels 4-9: 0 the segmented parser is not
+ * used, 1 in super-steps, 2 as a pipeline of segments (the default); fixed when the plan is created */
+I32 zsc_hip_deflate_plan_seg_schedule(const zsc_hip_deflate_plan *plan);
+
 void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *plan);
 
 /* device-resident inflate batches ------------------------------------------ */

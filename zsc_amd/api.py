@@ -104,6 +104,8 @@ def _load() -> C.CDLL:
     L.zsc_hip_deflate_plan_scratch_bytes.restype = C.c_uint64
     L.zsc_hip_deflate_plan_sub_batches.argtypes = [C.c_void_p]
     L.zsc_hip_deflate_plan_sub_batches.restype = C.c_uint32
+    L.zsc_hip_deflate_plan_seg_schedule.argtypes = [C.c_void_p]
+    L.zsc_hip_deflate_plan_seg_schedule.restype = C.c_int32
     L.zsc_hip_deflate_plan_destroy.argtypes = [C.c_void_p]
     L.zsc_hip_deflate_plan_destroy.restype = None
     return L
@@ -501,6 +503,11 @@ class DeflatePlan:
     @property
     def sub_batches(self) -> int:
         return lib.zsc_hip_deflate_plan_sub_batches(self._h)
+
+    @property
+    def seg_schedule(self) -> str:
+        """How long plain buffers are parsed at levels 4-9: "none", "super-steps" or "pipeline"."""
+        return ("none", "super-steps", "pipeline")[lib.zsc_hip_deflate_plan_seg_schedule(self._h)]
 
     def profile(self, enable: bool = True) -> None:
         lib.zsc_hip_deflate_plan_profile(self._h, 1 if enable else 0)

@@ -137,9 +137,13 @@ typedef struct {
     uint32_t it;        /* position of the current parse-loop iteration */
 } LzState;
 
+#ifndef LZ_RING_HOOK
+#define LZ_RING_HOOK(st, pos) /* host emulation: a ring index is being worked out for this position */
+#endif
 template <class L>
 DEV uint32_t lz_ridx(const LzState &st, uint32_t pos)
 {
+    LZ_RING_HOOK(st, pos);
     uint32_t r = pos - st.wrap_base;
     return r >= L::RING ? r - L::RING : r;
 }

@@ -34,6 +34,9 @@
  * The symbol stream, block records and therefore every later kernel and the final
  * bytes are identical to the wave-per-buffer parser's.  The search itself is described
  * further down (SG_EVAL, SG_SWEEP).
+ *
+ * The super-steps are the schedule of runs with joints.  Plain buffers run the same segment parser
+ * (sg_parse_segment<.., PIPE>) as a pipeline of segments without a barrier between them: lz_parse_pipe.h.
  */
 #ifndef ZSC_LZ_PARSE_SEG_H
 #define ZSC_LZ_PARSE_SEG_H
@@ -135,6 +138,17 @@ struct SgLds {
     uint32_t lo, hi, wrap_base;   /* window ring */
     SgOut out;
     uint32_t cstage[WAVE];
+    /* the pipeline schedule (lz_parse_pipe.h): segments are numbered through the whole buffer and
+     * segment g uses slot g % SG_NS of trace / tkind / wv and of the scratch */
+    uint32_t p_done[SG_NS];       /* g + 1 once the speculative parse of segment g is complete */
+    uint32_t p_next;              /* next segment to hand out */
+    uint32_t p_released;          /* every segment below this one has given its slot back */
+    uint32_t p_res_busy, p_load_busy; /* the resolver / the window loader is at work */
+    uint32_t p_redo;              /* 0: none, 1: wanted (redo_seg from the state in p_rs), 2: running */
+    uint32_t p_rs[4];             /* the exact state a redo starts from: p, len, at, pending */
+    uint32_t p_chain_xp;          /* the resolver entered segment `chain` at this position (chain_ft is
+                                     read from sidx once that segment is complete); 0xffffffff: chain_ft holds */
+    uint32_t p_stuck;
 };
 
 /* scratch in HBM per workgroup */
@@ -227,6 +241,23 @@ DEV void sg_phase_begin(const LzJob &job, SgLds *lds, int w)
             (&lds->trace[0][0])[i] = 0;
     }
     WAVE_SYNC();
+}
+
+/* ---- what the pipeline schedule (lz_parse_pipe.h) gives the parser in place of the super-step's state ----
+ *
+ * The ring holds position x at x % RING, whatever has been loaded since (lz_load_chunk keeps it so).  A
+ * parser that starts at p reads [p - wsize, p + SG_G + SG_OV + a lookahead or two): with the multiple of
+ * RING at or below p - wsize as its base, lz_ridx's one conditional wrap serves for all of them. */
+DEV uint32_t sg_pipe_wrap_base(uint32_t p)
+{
+    return p > ZD_TILE ? (p - ZD_TILE) / SgLds::RING * SgLds::RING : 0u;
+}
+/* A parser that has run past its segment may look for a hand-over in the segments whose slots hold their
+ * own traces or none yet: those below p_released + SG_NS (a slot is cleared before it is given back). */
+DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
+{
+    const uint64_t e = ((uint64_t)GUNI(LDS_LOAD_ACQ(&lds->p_released)) + SG_NS) * SG_G;
+    return e < n ? (uint32_t)e : n;
 }
 
 /* ---- the search ------------------------------------------------------------------
@@ -769,14 +800,14 @@ DEV void sg_phase_begin(const LzJob &job, SgLds *lds, int w)
             if (GRP >= 32u) {                                                                 \
                 for (uint32_t _j = 0; _j < GRP / 32u; _j++) {                                 \
                     const uint32_t _w = sd_blk * (GRP / 32u) + _j;                            \
-                    lds->tkind[s][_w] = (uint32_t)(_mk >> (32u * _j));                        \
-                    LDS_STORE_REL(&lds->trace[s][_w], (uint32_t)(_mf >> (32u * _j)));         \
+                    lds->tkind[slot][_w] = (uint32_t)(_mk >> (32u * _j));                        \
+                    LDS_STORE_REL(&lds->trace[slot][_w], (uint32_t)(_mf >> (32u * _j)));         \
                 }                                                                             \
             } else { /* (narrow groups: part of a word; this parser is the word's only writer) */ \
                 const uint32_t _w = sd_blk * GRP / 32u, _sh = sd_blk * GRP % 32u;             \
                 const uint32_t _m = ((1u << (GRP & 31u)) - 1u) << _sh;                        \
-                lds->tkind[s][_w] = (lds->tkind[s][_w] & ~_m) | ((uint32_t)_mk << _sh);       \
-                LDS_STORE_REL(&lds->trace[s][_w], (lds->trace[s][_w] & ~_m) | ((uint32_t)_mf << _sh)); \
+                lds->tkind[slot][_w] = (lds->tkind[slot][_w] & ~_m) | ((uint32_t)_mk << _sh);       \
+                LDS_STORE_REL(&lds->trace[slot][_w], (lds->trace[slot][_w] & ~_m) | ((uint32_t)_mf << _sh)); \
             }                                                                                 \
         }                                                                                     \
     } while (0)
@@ -801,7 +832,10 @@ DEV void sg_phase_begin(const LzJob &job, SgLds *lds, int w)
 /* parse from (p, cur_len, cur_at, pending) -- a state of the serial parse, or the fresh
  * state at the start of segment s -- until the parse can be handed to a later segment's
  * tokens, gives up, or leaves the super-step */
-template <bool TABLE> /* the buffer has a match table (job.r2): a build without it carries none of its code */
+/* PIPE (lz_parse_pipe.h): s is the segment's number in the whole buffer, its slot is s % SG_NS, the
+ * super-step is the whole buffer as far as slots have been given back, and the ring index is taken
+ * from the parser's own start so that it holds while the window slides under it */
+template <bool TABLE, bool PIPE = false> /* TABLE: the buffer has a match table (job.r2): a build without it carries none of its code */
 DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, uint32_t s,
                           uint32_t p, uint32_t cur_len, uint32_t cur_at, int pending)
 {
@@ -809,15 +843,17 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
     LzState st;
     st.lo = GUNI(lds->lo);
     st.hi = GUNI(lds->hi);
-    st.wrap_base = GUNI(lds->wrap_base);
+    st.wrap_base = PIPE ? sg_pipe_wrap_base(p) : GUNI(lds->wrap_base);
     st.nsyms = st.nstaged = st.nblocks = st.blk_sym0 = st.blk_in0 = st.pr_hi = 0;
     st.n = job.n;
     st.si = 0;
     st.it = 0;
 
-    const uint32_t S0 = GUNI(lds->S0);
+    const uint32_t slot = PIPE ? s % SG_NS : s;
+    const uint32_t S0 = PIPE ? 0u : GUNI(lds->S0);
     const uint64_t E64 = (uint64_t)S0 + SG_SPAN;
-    const uint32_t E = E64 < job.n ? (uint32_t)E64 : job.n; /* end of the super-step */
+    /* end of the super-step (PIPE: read when the parser leaves its segment, it only grows) */
+    uint32_t E = PIPE ? job.n : E64 < job.n ? (uint32_t)E64 : job.n;
     const uint32_t a_s = S0 + s * SG_G;
     const uint32_t e_s = a_s + SG_G < E ? a_s + SG_G : E;
 
@@ -826,8 +862,8 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
         uint64_t end = (uint64_t)st.base + 2ull * job.cfg.wsize;
         st.data_end = end < job.n ? (uint32_t)end : job.n;
     }
-    uint32_t *tok = scr.tok + s * SG_TOKCAP;
-    uint16_t *sidx = scr.sidx + s * SG_TRACE;
+    uint32_t *tok = scr.tok + slot * SG_TOKCAP;
+    uint16_t *sidx = scr.sidx + slot * SG_TRACE;
     uint32_t ntok = 0, nstaged = 0, exit_kind = 0;
 
     /* everything a search needs from memory that does not depend on the candidates is
@@ -877,6 +913,8 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
         /* no match pending: the state is (p, pending) alone -- fresh or neutral */
         const int fresh = cur_len == 2u;
         if (p >= e_s) {
+            if (PIPE)
+                E = sg_pipe_limit(lds, job.n);
             if (p >= E) {
                 exit_kind = SG_EXIT_LAST;
                 break;
@@ -885,9 +923,10 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 /* the segment p lies in recorded the positions its own parser was fresh at */
                 const uint32_t t = (p - S0) / SG_G, r = (p - S0) % SG_G;
                 /* (the other parser may still be running: its words are published kinds first) */
-                const uint32_t tword = GUNI(LDS_LOAD_ACQ(&lds->trace[t][r >> 5]));
+                const uint32_t ts = PIPE ? t % SG_NS : t;
+                const uint32_t tword = GUNI(LDS_LOAD_ACQ(&lds->trace[ts][r >> 5]));
                 if (((tword >> (r & 31u)) & 1u) &&
-                    ((GUNI(lds->tkind[t][r >> 5]) >> (r & 31u)) & 1u) == (uint32_t)pending) {
+                    ((GUNI(lds->tkind[ts][r >> 5]) >> (r & 31u)) & 1u) == (uint32_t)pending) {
                     exit_kind = SG_EXIT_SYNCED;
                     break;
                 }
@@ -1396,7 +1435,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
         SG_TRACE_FLUSH();
     ON_GLANE0
     {
-        SgWave *me = &lds->wv[s];
+        SgWave *me = &lds->wv[slot];
         me->exit_kind = exit_kind;
         me->exit_p = p;
         me->exit_len = cur_len;
@@ -1539,6 +1578,45 @@ DEV void sg_append(const LzJob &job, SgOut *o, const uint32_t *tok, uint32_t fro
     WAVE_SYNC();
 }
 
+/* the parse reached the end of the input at xp (src/deflate.c:2108-2117): the owed literal, the last
+ * block, and the counts the later kernels read (by the one wave that is resolving) */
+DEV void sg_end_of_input(const LzJob &job, SgLds *lds, uint32_t pending, uint32_t xp)
+{
+    if (pending) {
+        /* the last byte goes out as a literal; _tr_tally's "block full" answer is
+         * ignored here (src/deflate.c:2109-2112), so no cut */
+        const uint32_t c = UNI(job.in[xp - 1]);
+        ON_LANE0 { lds->cstage[0] = c; }
+        WAVE_SYNC();
+        sg_append(job, &lds->out, lds->cstage, 0, 1, 0, 1u, ZD_MIN_LOOKAHEAD);
+    }
+    ON_LANE0
+    {
+        /* a run of sections that is not the end of its stream: Z_FULL_FLUSH, the block only
+         * if it holds anything (src/deflate.c:2118-2120) */
+        const uint32_t cutting = !job.more || lds->out.nsyms != lds->out.blk_sym0;
+        if (cutting) {
+            ZdBlockRec *b = &job.blocks[lds->out.nblocks];
+            b->sym_begin = lds->out.blk_sym0;
+            b->sym_count = lds->out.nsyms - lds->out.blk_sym0;
+            b->in_begin = lds->out.blk_in0;
+            b->in_len = job.n - lds->out.blk_in0;
+            b->stored_ok = lds->out.blk_in0 >= sg_base(job.cfg, job.n, job.n) ? 1u : 0u;
+            b->last = job.more ? 0u : 1u;
+            b->cut = ZD_CUT_END;
+            b->wend = 0xffffffffu; /* at the end of the input everything given has been read */
+            b->at = job.n;
+            /* a run with joints goes on from here (sg_next_phase) */
+            lds->out.nblocks++;
+            lds->out.blk_sym0 = lds->out.nsyms;
+            lds->out.blk_in0 = job.n;
+        }
+        job.out->nsyms = lds->out.nsyms;
+        job.out->nblocks = lds->out.nblocks;
+    }
+    WAVE_SYNC();
+}
+
 /* phase 3 (wave 0): follow the chain of hand-overs from segment 0 and collect the
  * tokens; where a parser gave up, ask for a redo round and come back */
 DEV void sg_phase_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr, int w)
@@ -1583,38 +1661,10 @@ DEV void sg_phase_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr, in
             WAVE_SYNC();
             return;
         }
-        /* SG_EXIT_END: the parse reached the end of the input (src/deflate.c:2108-2117) */
-        if (UNI(lds->wv[k].exit_pending)) {
-            /* the last byte goes out as a literal; _tr_tally's "block full" answer is
-             * ignored here (src/deflate.c:2109-2112), so no cut */
-            const uint32_t c = UNI(job.in[xp - 1]);
-            ON_LANE0 { lds->cstage[0] = c; }
-            WAVE_SYNC();
-            sg_append(job, &lds->out, lds->cstage, 0, 1, 0, 1u, ZD_MIN_LOOKAHEAD);
-        }
+        /* SG_EXIT_END: the parse reached the end of the input */
+        sg_end_of_input(job, lds, UNI(lds->wv[k].exit_pending), xp);
         ON_LANE0
         {
-            /* a run of sections that is not the end of its stream: Z_FULL_FLUSH, the block only
-             * if it holds anything (src/deflate.c:2118-2120) */
-            const uint32_t cutting = !job.more || lds->out.nsyms != lds->out.blk_sym0;
-            if (cutting) {
-                ZdBlockRec *b = &job.blocks[lds->out.nblocks];
-                b->sym_begin = lds->out.blk_sym0;
-                b->sym_count = lds->out.nsyms - lds->out.blk_sym0;
-                b->in_begin = lds->out.blk_in0;
-                b->in_len = job.n - lds->out.blk_in0;
-                b->stored_ok = lds->out.blk_in0 >= sg_base(job.cfg, job.n, job.n) ? 1u : 0u;
-                b->last = job.more ? 0u : 1u;
-                b->cut = ZD_CUT_END;
-                b->wend = 0xffffffffu; /* at the end of the input everything given has been read */
-                b->at = job.n;
-                /* a run with joints goes on from here (sg_next_phase) */
-                lds->out.nblocks++;
-                lds->out.blk_sym0 = lds->out.nsyms;
-                lds->out.blk_in0 = job.n;
-            }
-            job.out->nsyms = lds->out.nsyms;
-            job.out->nblocks = lds->out.nblocks;
             lds->redo = 0;
             lds->finished = 1;
         }

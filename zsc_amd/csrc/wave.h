@@ -118,6 +118,15 @@ static inline uint32_t lds_u32(const uint8_t *base, uint32_t idx)
 #define GLOBAL_OR_U32(ptr, v) (*(ptr) |= (v))
 #define LDS_STORE_REL(ptr, v) (*(ptr) = (v))
 #define LDS_LOAD_ACQ(ptr) (*(ptr))
+static inline uint32_t emu_lds_cas(uint32_t *p, uint32_t expect, uint32_t v)
+{
+    const uint32_t old = *p;
+    if (old == expect)
+        *p = v;
+    return old;
+}
+#define LDS_CAS_U32(ptr, expect, v) emu_lds_cas((ptr), (expect), (v))
+#define WAVE_NAP(long_one) ((void)0)
 #define CTZ64(x) __builtin_ctzll(x)
 #define CTZ32(x) __builtin_ctz(x)
 #define POPC64(x) __builtin_popcountll(x)
@@ -250,6 +259,16 @@ DEV uint32_t lds_u32(const uint8_t *base, uint32_t idx)
  * what it stored to LDS before the release is there for whoever sees the new value */
 #define LDS_STORE_REL(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP)
 #define LDS_LOAD_ACQ(ptr) __hip_atomic_load((ptr), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)
+/* compare-and-swap on such a word (returns the old value): how one wave of the workgroup claims a piece
+ * of work; whoever wins it sees what the previous owner stored before giving it back */
+DEV uint32_t lds_cas_u32(uint32_t *p, uint32_t expect, uint32_t v)
+{
+    __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return expect;
+}
+#define LDS_CAS_U32(ptr, expect, v) lds_cas_u32((ptr), (expect), (v))
+/* a wave with nothing to do gets out of the way of the others for a moment */
+#define WAVE_NAP(long_one) ((long_one) ? __builtin_amdgcn_s_sleep(16) : __builtin_amdgcn_s_sleep(2))
 #define CTZ64(x) __builtin_ctzll(x)
 #define CTZ32(x) __builtin_ctz(x)
 #define POPC64(x) __builtin_popcountll(x)

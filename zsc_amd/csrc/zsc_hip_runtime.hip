@@ -30,6 +30,7 @@
 #include "inflate_resync.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
+#include "lz_parse_pipe.h"
 #include "match_table.h"
 #include "lz_parse_simple.h"
 #include "sections.h"
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(SG_W * 64, SG_MIN_WAVES) void k_parse_seg(const uin
                                                          uint32_t *__restrict__ seg_tok,
                                                          const ZdSched *__restrict__ sched,
                                                          const ZdLevel cfg, uint32_t stair_min,
-                                                         uint32_t first, uint32_t nbuf)
+                                                         uint32_t pipe, uint32_t first, uint32_t nbuf)
 {
     __shared__ SgLds lds;
     if (blockIdx.x >= nbuf)
@@ -364,6 +365,22 @@ __global__ __launch_bounds__(SG_W * 64, SG_MIN_WAVES) void k_parse_seg(const uin
     scr.tok = seg_tok + (uint64_t)blockIdx.x * SG_SCRATCH_WORDS;
     scr.sidx = (uint16_t *)(scr.tok + SG_NS * SG_TOKCAP);
     const int w = (int)(threadIdx.x >> 6);
+    if (pipe && buf.sched_n == 0) {
+        /* a plain buffer: the segments as a pipeline, no barrier between the first and the last of them
+         * (lz_parse_pipe.h); a run with joints keeps the super-steps below */
+        sg_pipe_init(&lds, w);
+        __syncthreads();
+        if (TABLE && job.r2 != nullptr)
+            sg_pipe_run<true>(job, &lds, scr);
+        else
+            sg_pipe_run<false>(job, &lds, scr);
+        __syncthreads();
+        if (lds.p_stuck && threadIdx.x == 0) {
+            job.out->nsyms = 0;
+            job.out->nblocks = 0xffffffffu; /* reported as Z_STREAM_ERROR by the layout kernel */
+        }
+        return;
+    }
     sg_init(&lds, w);
     __syncthreads();
     /* every loop is bounded so that a logic error can never hang the device: a phase needs
@@ -1013,6 +1030,11 @@ struct zsc_hip_deflate_plan {
     uint32_t stair_min = SG_STAIR_MIN; /* chains at least this long are searched as a staircase (lz_parse_seg.h) */
     DevBuf d_sched;               /* joints of runs of sections (sections.h) */
     bool use_seg = true;
+    /* read from the environment once, when the plan is made (A/B and debugging): a plan cannot get a mixed
+     * configuration and the launch path looks nothing up */
+    bool seg_pipe = true;     /* ZSC_HIP_SEG_PIPE=0: plain buffers in super-steps too (lz_parse_seg.h) */
+    bool link_kernel = false; /* ZSC_HIP_LINK_KERNEL: k_link_prev runs even where the parser could do without */
+    bool fast_ring = false;   /* ZSC_HIP_FAST_RING: levels 1-3 with the window in an LDS ring */
     DevBuf d_res; /* one ZdResult per buffer of the whole plan */
     uint64_t rank_base_off = 0;
     bool profile = false;
@@ -1251,6 +1273,10 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
     }
 
     pl->use_seg = getenv("ZSC_HIP_NO_SEG") == nullptr && kLevels[level].slow;
+    if (const char *e = getenv("ZSC_HIP_SEG_PIPE"))
+        pl->seg_pipe = atoi(e) != 0;
+    pl->link_kernel = getenv("ZSC_HIP_LINK_KERNEL") != nullptr;
+    pl->fast_ring = getenv("ZSC_HIP_FAST_RING") != nullptr;
     /* per-sub-batch descriptor arrays */
     for (SubBatch &sb : pl->subs) {
         std::vector<uint32_t> tile_owner(sb.ntiles), blk_owner(sb.nslots), order(sb.count);
@@ -1436,7 +1462,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
         /* Z_HUFFMAN_ONLY / Z_RLE look at no earlier data than the previous byte: no chains */
         const bool simple = pl->strategy == (uint32_t)Z_HUFFMAN_ONLY || pl->strategy == (uint32_t)Z_RLE;
         const bool link_in_parser = !simple && cfg.slow && sb.cseg == sb.count && !pl->use_table &&
-                                    getenv("ZSC_HIP_LINK_KERNEL") == nullptr; /* (the variable: A/B and debugging) */
+                                    !pl->link_kernel;
         if (!simple) {
             hipLaunchKernelGGL(k_hash_sort, dim3(sb.ntiles), dim3(HS_WAVES * 64), 0, st, in, bufs,
                                (const uint32_t *)sb.d_tile_owner.p, sorted, tmp_syms, rank, dir,
@@ -1481,7 +1507,8 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
                                    (const uint32_t *)cnt, link_in_parser ? (const uint16_t *)dir : nullptr,
                                    pl->use_table ? (const uint32_t *)pl->d_r2.p : nullptr, tmp_syms, recs,
                                    pout, (uint32_t *)pl->d_seg_tok.p,
-                                   (const ZdSched *)pl->d_sched.p, cfg, pl->stair_min, 0u, sb.cseg);
+                                   (const ZdSched *)pl->d_sched.p, cfg, pl->stair_min, pl->seg_pipe ? 1u : 0u, 0u,
+                                   sb.cseg);
             }
             if (pl->d_sched.p) { /* runs with joints: the parsers keep a hole map (lz_parse.h) */
                 ZSC_LAUNCH_PARSE(LzLdsJ, sb.cseg, sb.c36 - sb.cseg);
@@ -1498,7 +1525,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
             }
 #undef ZSC_LAUNCH_PARSE
         } else
-            hipLaunchKernelGGL(getenv("ZSC_HIP_FAST_RING") ? k_parse_fast<LzLdsFast> : k_parse_fast<LzLdsFastG>,
+            hipLaunchKernelGGL(pl->fast_ring ? k_parse_fast<LzLdsFast> : k_parse_fast<LzLdsFastG>,
                                dim3(sb.count), dim3(64), 0, st, in, bufs,
                                (const uint32_t *)sb.d_order.p, (const uint32_t *)sorted,
                                (const uint16_t *)rank, (const uint16_t *)hib, tmp_syms, recs,
@@ -1585,6 +1612,13 @@ extern "C" uint64_t zsc_hip_deflate_plan_scratch_bytes(const zsc_hip_deflate_pla
 extern "C" U32 zsc_hip_deflate_plan_sub_batches(const zsc_hip_deflate_plan *pl)
 {
     return pl ? (U32)pl->subs.size() : 0;
+}
+
+extern "C" I32 zsc_hip_deflate_plan_seg_schedule(const zsc_hip_deflate_plan *pl)
+{
+    if (!pl || !pl->use_seg)
+        return 0;
+    return pl->seg_pipe ? 2 : 1;
 }
 
 extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
