@@ -203,7 +203,8 @@ ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan **plan, U32
 /* after _results: per stream, the number of sections (or pieces, of a chunks plan) decoded in parallel;
  * 0 for streams the serial decoder produced (and for every stream of a plain plan) */
 ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *plan, U32 *sections);
-/* bytes of device scratch a sections or chunks plan holds beyond a plain plan's (0 for a plain plan) */
+/* bytes of device scratch a sections, chunks, resync or indexed plan holds beyond a plain plan's (0 for a
+ * plain plan) */
 uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_plan *plan);
 
 /* zsc_hip_uncompress_batch through a sections plan: the same signature and per-item semantics */
@@ -267,6 +268,124 @@ ZlibReturn zsc_hip_uncompress_resync_batch(U32 count, const U8 *const *sources, 
  * counts (one per inflate() call that returned Z_DATA_ERROR; it only warns of them).  0 for a stream
  * that decoded cleanly. */
 ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *plan, U32 *errors);
+
+/* seek-point indexes -------------------------------------------------------- */
+
+/* A chunks plan finds, on every run, where the chained pieces of a stream start, how long each one's
+ * output is and which bytes before its start it reads.  With the index enabled it can hand these facts
+ * out as one blob per stream, to be kept beside the archive; an indexed plan decodes from the blob with
+ * none of the discovery, and can decode a range out of the middle (zsc_amd/csrc/inflate_index.h,
+ * DESIGN.md section 10).
+ *
+ * The blob.  Little-endian, self-contained, version 1.  The density of the index is the exporting plan's
+ * chunk_bytes: one point per chained piece.
+ *   header, 48 bytes
+ *      0  u32  magic 0x4943535A ("ZSCI")
+ *      4  u32  format version, 1
+ *      8  u32  CRC-32 (the gzip polynomial) of blob[12 .. length)
+ *     12  i32  window_bits the stream was decoded with
+ *     16  u32  wrapper kind: 0 raw, 1 zlib, 2 gzip
+ *     20  u32  bit 0: the header is a gzip header; bits 8-12: log2 of the header's distance limit
+ *     24  u32  chunk_bytes of the exporting plan (at least 256)
+ *     28  u32  consumed: the trailer's end, as the plain plan reports it
+ *     32  u32  total output bytes
+ *     36  u32  byte offset of the trailer (consumed less 0 / 4 / 8 bytes for raw / zlib / gzip)
+ *     40  u32  number of points, at least 1
+ *     44  u32  reserved, 0
+ *   points, 32 bytes each, from offset 48, in chain order; the first is the stream's start
+ *      0  u64  where the piece starts, as a bit offset into the stream (0 for the first)
+ *      8  u64  where its window lies, as a byte offset into the blob
+ *     16  u32  output offset
+ *     20  u32  output length
+ *     24  u32  check value of the piece's own output: CRC-32 for gzip streams, Adler-32 for zlib and raw ones
+ *     28  u32  length of its window: how far the piece reaches before its start, at most 32 768 (0 for the first)
+ *   windows, from the end of the points to the end of the blob, in point order without gaps: the last
+ *   `window length` output bytes before each piece.
+ * A blob is valid if magic, version and CRC are right; the wrapper kind fits window_bits and the gzip bit;
+ * the points ascend strictly in bit offset and in chunk (bit offset / (8 * chunk_bytes)), so at most one
+ * lies in a chunk; the output offsets are the running sum of the lengths and end at the total; each window
+ * is no longer than 32 KiB or than the output before its piece, and lies where the layout above puts it;
+ * and the trailer's offset lies at or behind the last point. */
+typedef struct {
+    I32 window_bits;
+    U32 wrapper;        /* 0 raw, 1 zlib, 2 gzip */
+    U32 gzip;           /* the header is a gzip header */
+    U32 dist_limit;     /* the header's distance limit in bytes */
+    U32 chunk_bytes;
+    U32 consumed;
+    U32 total_out;
+    U32 trailer_offset;
+    U32 points;
+} zsc_hip_index_header;
+
+/* Host functions; none needs a device.  Z_OK, or Z_DATA_ERROR for a blob that is not valid. */
+ZlibReturn zsc_hip_index_validate(const U8 *blob, uint64_t len);
+ZlibReturn zsc_hip_index_info(const U8 *blob, uint64_t len, zsc_hip_index_header *info);
+/* The smallest run of whole pieces that covers output bytes [out_begin, out_begin + out_len): its first
+ * piece, the number of pieces, and the output range [piece_begin, piece_begin + piece_len) they produce
+ * (any of the four may be NULL).  Z_STREAM_ERROR for an empty range or one not inside the output. */
+ZlibReturn zsc_hip_index_range(const U8 *blob, uint64_t len, uint64_t out_begin, uint64_t out_len,
+                               U32 *first_piece, U32 *piece_count, U32 *piece_begin, U32 *piece_len);
+
+/* Export.  zsc_hip_inflate_plan_index_enable: chunks plans only (Z_STREAM_ERROR for any other kind),
+ * before _run.  A plan that never enables it launches, holds and returns what it always did; with it
+ * enabled the write pass takes the slice check values of raw streams too, and nothing else changes.
+ * _index_size and _index_export are valid after _results and before the next _run: Z_OK and the blob for
+ * a stream the run finished in parallel (zsc_hip_inflate_plan_sections > 0); Z_DATA_ERROR and 0 bytes for
+ * a stream the serial decoder produced; Z_BUF_ERROR (and *len the bytes needed) for a short cap.  The
+ * windows are gathered on the device into one buffer (temporary, sized by a prefix sum of their lengths),
+ * so a blob costs one device-to-host copy of records and one of windows. */
+ZlibReturn zsc_hip_inflate_plan_index_enable(zsc_hip_inflate_plan *plan, I32 enable);
+ZlibReturn zsc_hip_inflate_plan_index_size(zsc_hip_inflate_plan *plan, U32 stream, uint64_t *bytes);
+ZlibReturn zsc_hip_inflate_plan_index_export(zsc_hip_inflate_plan *plan, U32 stream, U8 *blob, uint64_t cap,
+                                             uint64_t *len);
+
+/* Indexed plans: the arguments of zsc_hip_inflate_plan_create, plus per stream a blob (indexes[i],
+ * index_lens[i]; indexes == NULL or indexes[i] == NULL: no index) and optionally a range of the output
+ * (range_begins[i], range_lens[i]; a NULL array or a length of all ones: the whole stream).  _run,
+ * _results, _destroy, zsc_hip_inflate_plan_sections (the pieces decoded from the index, or 0) and
+ * zsc_hip_inflate_plan_scratch_bytes work on it.  Create validates every blob on the host, uploads points
+ * and windows once and orders the pieces of all streams by output length, longest first.  A run decodes
+ * every piece into place from its point with its window (k_idx_write), combines the pieces' check values
+ * and compares them with the stream's trailer and ISIZE (k_sec_finish), and then runs the serial decoder
+ * over the plan (k_inflate): no scan, count, retry, resolve or window launch.
+ *
+ * Whole streams follow the rule of the sections and chunks plans: the path only ever reports a clean
+ * Z_OK, and every other stream is decoded serially from its start -- a blob that is not valid or belongs
+ * to another stream, source_lens[i] below the index's consumed, a window_bits other than the index's, a
+ * short dest_caps[i], a piece that does not stop exactly at the next point (the last: at the indexed
+ * trailer offset), produces another length or check value, reaches back further or less far than its
+ * window is long or beyond the header's distance limit, a header other than the index says, a trailer or
+ * ISIZE mismatch.  So status, output bytes and consumed equal the plain plan's for every stream and every
+ * blob, with one exception: a raw stream has no trailer, and a range is checked against the index alone,
+ * so for them an index whose windows and piece check values were altered consistently cannot be told
+ * from a true one.  For a raw stream or a range the index is trusted as the stream's source is; the
+ * blob's CRC guards against accidents, not against intent.
+ *
+ * Ranges: the item decodes only the pieces zsc_hip_index_range names, to dst_offsets[i]; dest_caps[i]
+ * must hold piece_len.  On success Z_OK, dest_len = piece_len, consumed = the byte behind the last bit
+ * read.  There is no serial fallback (the destination is not sized for one): any disagreement, or a
+ * stream without a valid index, gives Z_DATA_ERROR (Z_BUF_ERROR for a dest_caps[i] below piece_len) with
+ * dest_len 0 and consumed 0.  A range that is empty or not inside the output: Z_STREAM_ERROR at create.
+ *
+ * Whatever a blob holds, the device reads nothing outside the plan's own allocations: every offset is
+ * checked at create, and the windows lie packed in one buffer behind 32 KiB of zeros, each ending where
+ * a full window would, so a piece that reaches beyond its window's length (a distance is at most 32 768)
+ * reads that buffer's earlier bytes and fails.  Scratch, held from create to destroy: 64 bytes per piece,
+ * the windows' bytes plus 32 KiB, 32 bytes per chunk up to the last point a stream's pieces stop at, and
+ * 232 bytes per stream plus 32. */
+ZlibReturn zsc_hip_inflate_plan_create_indexed(zsc_hip_inflate_plan **plan, U32 count,
+                                               const U32 *source_lens, const uint64_t *src_offsets,
+                                               const U32 *dest_caps, const uint64_t *dst_offsets,
+                                               I32 window_bits, const U8 *const *indexes,
+                                               const uint64_t *index_lens, const uint64_t *range_begins,
+                                               const uint64_t *range_lens);
+/* zsc_hip_uncompress_batch through an indexed plan (whole streams only): the same signature and per-item
+ * semantics, plus the blobs */
+ZlibReturn zsc_hip_uncompress_indexed_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                            U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                            I32 window_bits, const U8 *const *indexes,
+                                            const uint64_t *index_lens);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,9 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
   found by trial;
 * :func:`uncompress_resync_batch` -- full-flush sections inflated in parallel, damaged streams
   resynchronised at the next flush marker as zsc_uncompress does;
+* :func:`build_indexes`, :func:`uncompress_indexed_batch`, :func:`index_info`, :func:`index_range` --
+  seek-point indexes: exported once from a chunks plan, then every later decode (or a range out of the
+  middle) without the discovery;
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -24,5 +27,6 @@ from .api import (  # noqa: F401
     compress, compress2, compress_gzip, uncompress, uncompress2, uncompress_gzip,
     compress_batch, compress_sections_batch, compress_sections_device, uncompress_batch, uncompress_sections_batch,
     uncompress_chunks_batch, uncompress_resync_batch, DeflatePlan, InflatePlan,
+    uncompress_indexed_batch, build_indexes, index_info, index_range,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

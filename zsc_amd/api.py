@@ -31,6 +31,13 @@ def build_library() -> None:
     subprocess.run(["make", "-s", "-C", os.path.join(_HERE, "csrc")], check=True)
 
 
+class IndexHeader(C.Structure):
+    """zsc_hip_index_header (include/zsc_hip.h)"""
+    _fields_ = [("window_bits", C.c_int32), ("wrapper", C.c_uint32), ("gzip", C.c_uint32),
+                ("dist_limit", C.c_uint32), ("chunk_bytes", C.c_uint32), ("consumed", C.c_uint32),
+                ("total_out", C.c_uint32), ("trailer_offset", C.c_uint32), ("points", C.c_uint32)]
+
+
 def _load() -> C.CDLL:
     # PyTorch-ROCm wheels bundle their own libamdhip64 (SONAME libamdhip64.so.7, the same
     # as /opt/rocm's).  Two HIP runtimes in one process cannot both own the GPU, so when
@@ -87,6 +94,15 @@ def _load() -> C.CDLL:
     L.zsc_hip_inflate_plan_create_resync.argtypes = L.zsc_hip_inflate_plan_create_sections.argtypes
     L.zsc_hip_uncompress_resync_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes
     L.zsc_hip_inflate_plan_data_errors.argtypes = [C.c_void_p, u32p]
+    L.zsc_hip_index_validate.argtypes = [C.c_char_p, C.c_uint64]
+    L.zsc_hip_index_info.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(IndexHeader)]
+    L.zsc_hip_index_range.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, u32p, u32p, u32p, u32p]
+    L.zsc_hip_inflate_plan_index_enable.argtypes = [C.c_void_p, C.c_int32]
+    L.zsc_hip_inflate_plan_index_size.argtypes = [C.c_void_p, C.c_uint32, u64p]
+    L.zsc_hip_inflate_plan_index_export.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, u64p]
+    L.zsc_hip_inflate_plan_create_indexed.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p, u64p,
+                                                      C.c_int32, C.POINTER(C.c_char_p), u64p, u64p, u64p]
+    L.zsc_hip_uncompress_indexed_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes + [C.POINTER(C.c_char_p), u64p]
     L.zsc_hip_inflate_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.zsc_hip_inflate_plan_results.argtypes = [C.c_void_p, u32p, u32p, i32p, C.POINTER(C.c_float)]
     L.zsc_hip_inflate_plan_destroy.argtypes = [C.c_void_p]
@@ -355,6 +371,59 @@ def uncompress_resync_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
     return _uncompress_batch(lib.zsc_hip_uncompress_resync_batch, sources, dest_caps, window_bits)
 
 
+def uncompress_indexed_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
+                             indexes: Sequence[Optional[bytes]], window_bits: int = DEF_WBITS):
+    """zsc_hip_uncompress_indexed_batch: as uncompress_batch, with every stream that has a valid index
+    (export_index / build_indexes; None: no index) decoded in parallel from its seek points, without the
+    chunks plan's discovery (results identical to uncompress_batch for every input and every blob, but
+    see include/zsc_hip.h on raw streams)."""
+    count = len(sources)
+    blobs = (C.c_char_p * count)(*indexes)
+    blens = (C.c_uint64 * count)(*[len(b) if b is not None else 0 for b in indexes])
+    return _uncompress_batch(lambda *a: lib.zsc_hip_uncompress_indexed_batch(*a, blobs, blens), sources, dest_caps,
+                             window_bits)
+
+
+def index_info(blob: bytes) -> dict:
+    """zsc_hip_index_info: the header of a seek-point index as a dict (ValueError for a blob that is not
+    a valid index).  No device needed."""
+    h = IndexHeader()
+    if lib.zsc_hip_index_info(blob, len(blob), C.byref(h)) != Z_OK:
+        raise ValueError("not a valid seek-point index")
+    return {name: getattr(h, name) for name, _ in IndexHeader._fields_}
+
+
+def index_range(blob: bytes, begin: int, length: int) -> Tuple[int, int, int, int]:
+    """zsc_hip_index_range: (first piece, piece count, piece_begin, piece_len) of the smallest run of whole
+    pieces that covers output bytes [begin, begin + length).  ValueError for a blob that is not valid or a
+    range that is empty or not inside the output.  No device needed."""
+    f, c, b, n = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = lib.zsc_hip_index_range(blob, len(blob), begin, length, C.byref(f), C.byref(c), C.byref(b), C.byref(n))
+    if rc != Z_OK:
+        raise ValueError("not a valid seek-point index" if rc == Z_DATA_ERROR else "range outside the output")
+    return f.value, c.value, b.value, n.value
+
+
+def build_indexes(sources: Sequence[bytes], dest_caps: Sequence[int], window_bits: int = DEF_WBITS,
+                  chunk_bytes: int = 0) -> List[Optional[bytes]]:
+    """The seek-point index of every stream, from one run of a chunks plan with keep_index (None for a
+    stream the serial decoder produced: too short, damaged, or not split)."""
+    import torch
+    plan = InflatePlan([len(s) for s in sources], dest_caps, window_bits=window_bits, chunks=True,
+                       chunk_bytes=chunk_bytes, keep_index=True)
+    try:
+        src = torch.zeros(plan.src_bytes, dtype=torch.uint8, device="cuda")
+        dst = torch.empty(plan.dst_bytes, dtype=torch.uint8, device="cuda")
+        for s, off in zip(sources, plan.src_offsets):
+            if s:
+                src[off:off + len(s)] = torch.frombuffer(bytearray(s), dtype=torch.uint8).cuda()
+        plan.run(src.data_ptr(), dst.data_ptr())
+        plan.results()
+        return [plan.export_index(i) for i in range(len(sources))]
+    finally:
+        plan.close()
+
+
 def _uncompress_batch(fn, sources, dest_caps, window_bits):
     count = len(sources)
     srcs = (C.c_char_p * count)(*sources)
@@ -375,12 +444,24 @@ class InflatePlan:
     than chunk_bytes decoded in parallel pieces; chunk_bytes 0 = the library's default; no decode_order
     either).  resync=True makes a resync plan (zsc_hip_inflate_plan_create_resync: a sections plan that
     also decodes damaged streams in parallel, resynchronising at the next flush marker after a data
-    error); it implies sections."""
+    error); it implies sections.  keep_index=True (chunks plans only) keeps what a run finds out, for
+    export_index().  indexes=[blob or None, ...] makes an indexed plan (zsc_hip_inflate_plan_create_indexed:
+    every stream with a valid index decoded in parallel from its seek points); with it, ranges=[(begin,
+    length) or None, ...] decodes only the whole pieces that cover that range of the stream's output
+    (index_range), to the start of the stream's destination."""
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int],
                  window_bits: int = DEF_WBITS, decode_order: Sequence[int] | None = None,
-                 sections: bool = False, chunks: bool = False, chunk_bytes: int = 0, resync: bool = False):
+                 sections: bool = False, chunks: bool = False, chunk_bytes: int = 0, resync: bool = False,
+                 keep_index: bool = False, indexes: Sequence[Optional[bytes]] | None = None,
+                 ranges: Sequence[Optional[Tuple[int, int]]] | None = None):
         self.count = n = len(source_lens)
+        if keep_index and not chunks:
+            raise ValueError("keep_index needs a chunks plan")
+        if ranges is not None and indexes is None:
+            raise ValueError("ranges need indexes")
+        if indexes is not None and (sections or chunks or resync or decode_order is not None):
+            raise ValueError("an indexed plan is no sections, chunks or resync plan and takes no decode_order")
         so, do, sb, db = [], [], 0, 0
         for sl, dc in zip(source_lens, dest_caps):
             so.append(sb)
@@ -394,7 +475,19 @@ class InflatePlan:
             raise ValueError("a resync plan is a sections plan, not a chunks plan")
         if sections and chunks:
             raise ValueError("a plan is a sections plan or a chunks plan, not both")
-        if chunks:
+        if indexes is not None:
+            if len(indexes) != n or (ranges is not None and len(ranges) != n):
+                raise ValueError("one index (and one range) per stream")
+            blobs = (C.c_char_p * n)(*indexes)
+            blens = (C.c_uint64 * n)(*[len(b) if b is not None else 0 for b in indexes])
+            rb = rl = None
+            if ranges is not None:
+                rb = (C.c_uint64 * n)(*[r[0] if r is not None else 0 for r in ranges])
+                rl = (C.c_uint64 * n)(*[r[1] if r is not None else 0xffffffffffffffff for r in ranges])
+            rc = lib.zsc_hip_inflate_plan_create_indexed(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
+                                                         (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
+                                                         (C.c_uint64 * n)(*do), window_bits, blobs, blens, rb, rl)
+        elif chunks:
             if decode_order is not None:
                 raise ValueError("a chunks plan takes no decode_order")
             rc = lib.zsc_hip_inflate_plan_create_chunks(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
@@ -414,6 +507,24 @@ class InflatePlan:
                                                          (C.c_uint64 * n)(*do), window_bits, order)
         if rc != Z_OK:
             raise RuntimeError(f"zsc_hip_inflate_plan_create failed: {rc}")
+        if keep_index and lib.zsc_hip_inflate_plan_index_enable(self._h, 1) != Z_OK:
+            raise RuntimeError("zsc_hip_inflate_plan_index_enable failed")
+
+    def export_index(self, i: int) -> Optional[bytes]:
+        """After results() of a chunks plan made with keep_index: the seek-point index of stream i, or
+        None for a stream the serial decoder produced."""
+        need = C.c_uint64()
+        rc = lib.zsc_hip_inflate_plan_index_size(self._h, i, C.byref(need))
+        if rc == Z_DATA_ERROR:
+            return None
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_index_size failed: {rc}")
+        buf = C.create_string_buffer(need.value)
+        got = C.c_uint64()
+        rc = lib.zsc_hip_inflate_plan_index_export(self._h, i, buf, need.value, C.byref(got))
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_index_export failed: {rc}")
+        return buf.raw[:got.value]
 
     def run(self, d_src: int, d_dst: int, stream: int = 0) -> None:
         rc = lib.zsc_hip_inflate_plan_run(self._h, C.c_void_p(d_src), C.c_void_p(d_dst),

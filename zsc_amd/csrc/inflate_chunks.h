@@ -75,6 +75,7 @@ typedef struct {
     uint8_t *win;      /* per chunk: INF_WIN bytes, the window of a chained piece */
     uint32_t nactive;  /* streams with more than one chunk (P.sp.active) */
     uint32_t chunk_bytes;
+    uint32_t keep_index; /* the write pass takes the slice check values of raw streams too (inflate_index.h) */
 } IchkPlan;
 
 /* ---- whole-wave code: setup and scan ---- */
@@ -517,7 +518,7 @@ DEV void chk_write_worker(const IchkPlan &P, const uint8_t *src_all, uint8_t *ds
                           (outcome == INF_SEC_FINAL && link == SEC_LINK_FIN &&
                            start + GUNI(si->stop) == GUNI(P.sp.cstop[cb + k])));
         uint32_t ck = 0;
-        if (P.sp.window_bits >= 0) {
+        if (P.sp.window_bits >= 0 || P.keep_index) {
             SEC_FENCE();
             ck = (GUNI(S->head) & 1u) ? INF_CK(crc32_tx)<1>(dst, len, lds->cktab, INF_CKX(lds))
                                       : INF_CK(adler32)(dst, len);

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <map>
 #include <vector>
 
 #include "bit_emit.h"
@@ -28,6 +29,7 @@
 #include "inflate_sections.h"
 #include "inflate_chunks.h"
 #include "inflate_resync.h"
+#include "inflate_index.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "lz_parse_pipe.h"
@@ -772,6 +774,70 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU
     if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
         lds_all[grp].cktab = crc_table;
     chk_write_worker(P, src, dst, &lds_all[grp], &info[grp], &piece[grp]);
+}
+
+/* kernel 9 (inflate_index.h): streams inflated from a seek-point index -- one launch ahead of
+ * k_sec_finish and k_inflate */
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_idx_write(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, IidxPlan P, InfResult *__restrict__ res,
+    InfResume *__restrict__ resume)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    idx_write_worker(P, src, dst, &lds_all[grp], &info[grp], &piece[grp], res, resume);
+}
+
+/* the export of a chunks plan's index: the records of stream s's chain, each window's place in the
+ * gathered buffer by a prefix sum of the window lengths (one workgroup, IDX_REC_THREADS records a step);
+ * then the windows, cut down to what their pieces reach, copied to their places */
+#define IDX_REC_THREADS 1024
+__global__ __launch_bounds__(IDX_REC_THREADS) void k_idx_records(IchkPlan P, uint32_t s, uint32_t n, ZidxRec *recs,
+                                                                 uint64_t *total)
+{
+    __shared__ uint32_t sc[IDX_REC_THREADS];
+    __shared__ uint64_t carry;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0)
+        carry = 0;
+    __syncthreads();
+    for (uint32_t b = 0; b < n; b += IDX_REC_THREADS) {
+        const uint32_t i = b + tid;
+        ZidxRec r = {};
+        if (i < n)
+            idx_record(P, s, i, &r);
+        sc[tid] = r.wlen;
+        __syncthreads();
+        for (uint32_t d = 1; d < IDX_REC_THREADS; d <<= 1) {
+            const uint32_t v = tid >= d ? sc[tid - d] : 0u;
+            __syncthreads();
+            sc[tid] += v;
+            __syncthreads();
+        }
+        if (i < n) {
+            r.woff = carry + (sc[tid] - r.wlen);
+            recs[i] = r;
+        }
+        __syncthreads();
+        if (tid == IDX_REC_THREADS - 1u)
+            carry += sc[tid];
+        __syncthreads();
+    }
+    if (tid == 0)
+        *total = carry;
+}
+
+#define IDX_GATHER_THREADS 256
+__global__ __launch_bounds__(IDX_GATHER_THREADS) void k_idx_gather(IchkPlan P, uint32_t s, uint32_t n,
+                                                                   const ZidxRec *__restrict__ recs,
+                                                                   uint8_t *__restrict__ out)
+{
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
+        idx_gather(P, s, i, &recs[i], out, threadIdx.x, IDX_GATHER_THREADS);
 }
 
 /* kernel 8 (inflate_resync.h): damaged full-flush streams inflated in parallel, with inflateSync's
@@ -2523,6 +2589,14 @@ struct zsc_hip_inflate_plan {
     bool resync = false;
     IrsyPlan rp = {};
     DevBuf d_cerr, d_chain_fl, d_rst;
+    /* indexed plans only (inflate_index.h; they also use d_sitems, d_sst, d_active, d_q, d_nsec, d_clen,
+     * d_chain_k, d_chain_ck, d_cand and d_win) */
+    bool indexed = false, idx_fixed = false;
+    IidxPlan ip = {};
+    uint32_t idx_active = 0;
+    DevBuf d_sst0, d_q0, d_ipieces, d_iunits, d_ixs, d_idone, d_res0, d_resume0;
+    /* chunks plans with the index enabled: the records of the streams asked for since the last run */
+    std::map<uint32_t, std::pair<std::vector<ZidxRec>, uint64_t>> idx_recs;
     const void *last_src = nullptr;
     void *last_dst = nullptr;
     hipStream_t last_stream = nullptr;
@@ -2617,7 +2691,8 @@ static void inflate_plan_release(zsc_hip_inflate_plan *pl)
                       &pl->d_tiles, &pl->d_tile_cnt, &pl->d_tile_off, &pl->d_scount, &pl->d_nsec, &pl->d_sst,
                       &pl->d_active, &pl->d_q, &pl->d_cstart, &pl->d_cstop, &pl->d_clink, &pl->d_clen,
                       &pl->d_chain_k, &pl->d_chain_off, &pl->d_chain_ck, &pl->d_cand, &pl->d_cused, &pl->d_creach,
-                      &pl->d_want, &pl->d_ring, &pl->d_win, &pl->d_cerr, &pl->d_chain_fl, &pl->d_rst})
+                      &pl->d_want, &pl->d_ring, &pl->d_win, &pl->d_cerr, &pl->d_chain_fl, &pl->d_rst, &pl->d_sst0,
+                      &pl->d_q0, &pl->d_ipieces, &pl->d_iunits, &pl->d_ixs, &pl->d_idone, &pl->d_res0, &pl->d_resume0})
         b->release();
 }
 
@@ -2827,6 +2902,136 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_resync(zsc_hip_inflate_plan **
     return Z_OK;
 }
 
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_indexed(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                          const U32 *source_lens, const uint64_t *src_offsets,
+                                                          const U32 *dest_caps, const uint64_t *dst_offsets,
+                                                          I32 window_bits, const U8 *const *indexes,
+                                                          const uint64_t *index_lens, const uint64_t *range_begins,
+                                                          const uint64_t *range_lens)
+{
+    ZSC_ASSERT(plan_out != Z_NULL);
+    *plan_out = nullptr;
+    /* the blobs are checked and the tables built on the host before anything is allocated */
+    IdxBuild B;
+    for (U32 i = 0; i < count; i++) {
+        const bool ranged = range_begins && range_lens && range_lens[i] != ~0ull;
+        const U8 *blob = indexes && index_lens ? indexes[i] : Z_NULL;
+        if (B.add(source_lens[i], src_offsets[i], dest_caps[i], dst_offsets[i], window_bits, blob,
+                  blob ? index_lens[i] : 0, ranged, ranged ? range_begins[i] : 0, ranged ? range_lens[i] : 0) != 0) {
+            ZSC_WARN1("zsc_hip: the range of stream %u is not inside its output.", i);
+            return Z_STREAM_ERROR;
+        }
+    }
+    B.finish();
+    if (B.pieces.size() >= 0xffffffffull)
+        return Z_MEM_ERROR;
+    ZlibReturn rc = zsc_hip_inflate_plan_create(plan_out, count, source_lens, src_offsets, dest_caps, dst_offsets,
+                                                window_bits);
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    zsc_hip_inflate_plan *pl = *plan_out;
+    pl->indexed = true;
+    pl->idx_fixed = B.any_fixed;
+    pl->idx_active = (uint32_t)B.active.size();
+    const uint64_t nc = std::max<uint64_t>(1, count), np = std::max<uint64_t>(1, B.pieces.size());
+    const uint64_t ncand = std::max<uint64_t>(1, B.cand.size());
+    const uint32_t q0[4] = {pl->idx_active, 0, 0, 0};
+    std::vector<InfResume> resume0(nc);
+    memset(resume0.data(), 0, sizeof(InfResume) * nc);
+    for (U32 i = 0; i < count; i++)
+        resume0[i].state = B.state0[i];
+    struct Up {
+        DevBuf *buf;
+        const void *from;
+        uint64_t bytes, have;
+    };
+    const Up ups[] = {
+        {&pl->d_sitems, B.items.data(), sizeof(IsecItem) * nc, sizeof(IsecItem) * count},
+        {&pl->d_sst0, B.st.data(), sizeof(IsecStream) * nc, sizeof(IsecStream) * count},
+        {&pl->d_sst, nullptr, sizeof(IsecStream) * nc, 0},
+        {&pl->d_ixs, B.xs.data(), sizeof(IdxStream) * nc, sizeof(IdxStream) * count},
+        {&pl->d_active, B.active.data(), 4 * nc, 4ull * B.active.size()},
+        {&pl->d_q0, q0, 16, 16},
+        {&pl->d_q, nullptr, 16, 0},
+        {&pl->d_nsec, nullptr, 4 * nc, 0},
+        {&pl->d_idone, nullptr, 4 * nc, 0},
+        {&pl->d_res0, B.res0.data(), sizeof(InfResult) * nc, sizeof(InfResult) * count},
+        {&pl->d_resume0, resume0.data(), sizeof(InfResume) * nc, sizeof(InfResume) * count},
+        {&pl->d_ipieces, B.pieces.data(), sizeof(IdxPiece) * np, sizeof(IdxPiece) * B.pieces.size()},
+        {&pl->d_iunits, B.units.data(), 4 * np, 4ull * B.units.size()},
+        {&pl->d_clen, B.clen.data(), 4 * np, 4ull * B.clen.size()},
+        {&pl->d_chain_k, B.chain_k.data(), 4 * np, 4ull * B.chain_k.size()},
+        {&pl->d_chain_ck, nullptr, 4 * np, 0},
+        {&pl->d_cand, B.cand.data(), 8 * ncand, 8ull * B.cand.size()},
+        {&pl->d_win, B.win.data(), B.win.size(), B.win.size()},
+    };
+    bool ok = true;
+    pl->scratch_bytes = 0;
+    for (const Up &u : ups) {
+        ok = ok && u.buf->ensure(u.bytes);
+        if (ok && u.have)
+            ok = hipMemcpy(u.buf->p, u.from, u.have, hipMemcpyHostToDevice) == hipSuccess;
+        pl->scratch_bytes += u.bytes;
+    }
+    if (!ok) {
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    IidxPlan &P = pl->ip;
+    P.sp.items = (const IsecItem *)pl->d_sitems.p;
+    P.sp.nsec = (uint32_t *)pl->d_nsec.p;
+    P.sp.st = (IsecStream *)pl->d_sst.p;
+    P.sp.active = (uint32_t *)pl->d_active.p;
+    P.sp.q = (uint32_t *)pl->d_q.p;
+    P.sp.clen = (uint32_t *)pl->d_clen.p;
+    P.sp.chain_k = (uint32_t *)pl->d_chain_k.p;
+    P.sp.chain_ck = (uint32_t *)pl->d_chain_ck.p;
+    P.sp.count = count;
+    P.sp.window_bits = window_bits;
+    P.pieces = (const IdxPiece *)pl->d_ipieces.p;
+    P.units = (const uint32_t *)pl->d_iunits.p;
+    P.xs = (const IdxStream *)pl->d_ixs.p;
+    P.done = (uint32_t *)pl->d_idone.p;
+    P.cand = (const uint64_t *)pl->d_cand.p;
+    P.win = (const uint8_t *)pl->d_win.p;
+    P.nunits = (uint32_t)B.units.size();
+    pl->ncand_total = B.units.size();
+    return Z_OK;
+}
+
+/* the launches of an indexed plan, ahead of k_inflate: the state every run starts from, the write
+ * pass, finish */
+static ZlibReturn idx_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
+{
+    const IidxPlan &P = pl->ip;
+    HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+    if (pl->idx_fixed) {
+        HIP_TRY(hipMemcpyAsync(pl->d_res.p, pl->d_res0.p, sizeof(InfResult) * pl->count, hipMemcpyDeviceToDevice, st),
+                return Z_STREAM_ERROR);
+        HIP_TRY(hipMemcpyAsync(pl->d_resume.p, pl->d_resume0.p, sizeof(InfResume) * pl->count,
+                               hipMemcpyDeviceToDevice, st),
+                return Z_STREAM_ERROR);
+    }
+    if (P.nunits == 0)
+        return Z_OK;
+    HIP_TRY(hipMemsetAsync(pl->d_idone.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+    HIP_TRY(hipMemcpyAsync(pl->d_sst.p, pl->d_sst0.p, sizeof(IsecStream) * pl->count, hipMemcpyDeviceToDevice, st),
+            return Z_STREAM_ERROR);
+    HIP_TRY(hipMemcpyAsync(pl->d_q.p, pl->d_q0.p, 16, hipMemcpyDeviceToDevice, st), return Z_STREAM_ERROR);
+    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
+    const uint32_t groups = std::max(1u, std::min(fill, (P.nunits + INF_PER_WAVE - 1) / INF_PER_WAVE));
+    hipLaunchKernelGGL(k_idx_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P,
+                       (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+    if (pl->idx_active) {
+        const uint32_t per_stream = std::max(1u, std::min(pl->idx_active, fill));
+        hipLaunchKernelGGL(k_sec_finish, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
+                           (const uint8_t *)d_src, P.sp, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+    }
+    return Z_OK;
+}
+
 /* the launches of a chunks plan, ahead of k_inflate (none when no stream is longer than a chunk) */
 static void chk_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
 {
@@ -2916,8 +3121,12 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         rsy_enqueue(pl, d_src, d_dst, st);
     else if (pl->sections)
         sec_enqueue(pl, d_src, d_dst, st);
-    if (pl->chunks)
+    if (pl->chunks) {
+        pl->idx_recs.clear();
         chk_enqueue(pl, d_src, d_dst, st);
+    }
+    if (pl->indexed && idx_enqueue(pl, d_src, d_dst, st) != Z_OK)
+        return Z_STREAM_ERROR;
     hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, st, (const uint8_t *)d_src,
                        (uint8_t *)d_dst, (const ZdInfItem *)pl->d_items.p,
                        (const uint32_t *)pl->d_order.p, (InfResult *)pl->d_res.p,
@@ -2993,7 +3202,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U3
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     ZSC_ASSERT(sections != Z_NULL);
-    if (!(pl->sections || pl->chunks) || !pl->last_dst || pl->count == 0) {
+    if (!(pl->sections || pl->chunks || pl->indexed) || !pl->last_dst || pl->count == 0) {
         for (uint32_t i = 0; i < pl->count; i++)
             sections[i] = 0;
         return Z_OK;
@@ -3022,13 +3231,167 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *pl,
     return Z_OK;
 }
 
+extern "C" ZlibReturn zsc_hip_inflate_plan_index_enable(zsc_hip_inflate_plan *pl, I32 enable)
+{
+    ZSC_ASSERT(pl != Z_NULL);
+    if (!pl->chunks)
+        return Z_STREAM_ERROR;
+    pl->cp.keep_index = enable ? 1u : 0u;
+    return Z_OK;
+}
+
+/* the records of stream `stream` of the last run (kept until the next one); Z_DATA_ERROR: no index */
+static ZlibReturn idx_records(zsc_hip_inflate_plan *pl, U32 stream, const std::vector<ZidxRec> **recs,
+                              uint64_t *wbytes)
+{
+    if (!pl->chunks || !pl->cp.keep_index || stream >= pl->count || !pl->last_dst)
+        return Z_STREAM_ERROR;
+    auto hit = pl->idx_recs.find(stream);
+    if (hit == pl->idx_recs.end()) {
+        HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+        uint32_t n = 0;
+        HIP_TRY(hipMemcpy(&n, (const uint32_t *)pl->d_nsec.p + stream, 4, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+        std::vector<ZidxRec> r(n);
+        uint64_t total = 0;
+        if (n) {
+            DevBuf d_recs, d_total;
+            bool ok = d_recs.ensure(sizeof(ZidxRec) * n) && d_total.ensure(8);
+            if (ok) {
+                hipLaunchKernelGGL(k_idx_records, dim3(1), dim3(IDX_REC_THREADS), 0, pl->last_stream, pl->cp, stream, n,
+                                   (ZidxRec *)d_recs.p, (uint64_t *)d_total.p);
+                ok = hipStreamSynchronize(pl->last_stream) == hipSuccess &&
+                     hipMemcpy(r.data(), d_recs.p, sizeof(ZidxRec) * n, hipMemcpyDeviceToHost) == hipSuccess &&
+                     hipMemcpy(&total, d_total.p, 8, hipMemcpyDeviceToHost) == hipSuccess;
+            }
+            d_recs.release();
+            d_total.release();
+            if (!ok)
+                return Z_MEM_ERROR;
+        }
+        hit = pl->idx_recs.emplace(stream, std::make_pair(std::move(r), total)).first;
+    }
+    *recs = &hit->second.first;
+    *wbytes = hit->second.second;
+    return (*recs)->empty() ? Z_DATA_ERROR : Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_index_size(zsc_hip_inflate_plan *pl, U32 stream, uint64_t *bytes)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(bytes != Z_NULL);
+    *bytes = 0;
+    const std::vector<ZidxRec> *recs = nullptr;
+    uint64_t wbytes = 0;
+    const ZlibReturn rc = idx_records(pl, stream, &recs, &wbytes);
+    if (rc == Z_OK)
+        *bytes = zidx_blob_bytes((uint32_t)recs->size(), wbytes);
+    return rc;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_index_export(zsc_hip_inflate_plan *pl, U32 stream, U8 *blob, uint64_t cap,
+                                                        uint64_t *len)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(len != Z_NULL);
+    *len = 0;
+    const std::vector<ZidxRec> *recs = nullptr;
+    uint64_t wbytes = 0;
+    const ZlibReturn rc = idx_records(pl, stream, &recs, &wbytes);
+    if (rc != Z_OK)
+        return rc;
+    const uint32_t n = (uint32_t)recs->size();
+    const uint64_t bytes = zidx_blob_bytes(n, wbytes);
+    *len = bytes;
+    if (cap < bytes || blob == Z_NULL)
+        return Z_BUF_ERROR;
+    IsecStream S;
+    InfResult res;
+    HIP_TRY(hipMemcpy(&S, (const IsecStream *)pl->d_sst.p + stream, sizeof S, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    HIP_TRY(hipMemcpy(&res, (const InfResult *)pl->d_res.p + stream, sizeof res, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    if (wbytes) {
+        /* the windows, gathered on the device, in one copy */
+        DevBuf d_recs, d_wins;
+        bool ok = d_recs.ensure(sizeof(ZidxRec) * n) && d_wins.ensure(wbytes) &&
+                  hipMemcpy(d_recs.p, recs->data(), sizeof(ZidxRec) * n, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) {
+            const uint32_t blocks = std::max(1u, std::min(n, (uint32_t)g_cus * 8u));
+            hipLaunchKernelGGL(k_idx_gather, dim3(blocks), dim3(IDX_GATHER_THREADS), 0, pl->last_stream, pl->cp, stream, n,
+                               (const ZidxRec *)d_recs.p, (uint8_t *)d_wins.p);
+            ok = hipStreamSynchronize(pl->last_stream) == hipSuccess &&
+                 hipMemcpy(blob + zidx_blob_bytes(n, 0), d_wins.p, wbytes, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        d_recs.release();
+        d_wins.release();
+        if (!ok)
+            return Z_MEM_ERROR;
+    }
+    ZidxInfo h;
+    h.window_bits = pl->window_bits;
+    h.kind = pl->window_bits < 0 ? 0u : (S.head & 1u) ? 2u : 1u;
+    h.head = S.head;
+    h.chunk_bytes = pl->cp.chunk_bytes;
+    h.consumed = res.consumed;
+    h.total = S.total;
+    h.trailer = S.trailer;
+    h.npoints = n;
+    zidx_write_head(blob, &h, recs->data());
+    zidx_seal(blob, bytes);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_index_validate(const U8 *blob, uint64_t len)
+{
+    return zidx_validate(blob, len, nullptr) ? Z_OK : Z_DATA_ERROR;
+}
+
+extern "C" ZlibReturn zsc_hip_index_info(const U8 *blob, uint64_t len, zsc_hip_index_header *info)
+{
+    ZSC_ASSERT(info != Z_NULL);
+    ZidxInfo h;
+    if (!zidx_validate(blob, len, &h))
+        return Z_DATA_ERROR;
+    info->window_bits = h.window_bits;
+    info->wrapper = h.kind;
+    info->gzip = h.head & 1u;
+    info->dist_limit = 1u << ((h.head >> 8) & 31u);
+    info->chunk_bytes = h.chunk_bytes;
+    info->consumed = h.consumed;
+    info->total_out = h.total;
+    info->trailer_offset = h.trailer;
+    info->points = h.npoints;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_index_range(const U8 *blob, uint64_t len, uint64_t out_begin, uint64_t out_len,
+                                          U32 *first_piece, U32 *piece_count, U32 *piece_begin, U32 *piece_len)
+{
+    ZidxInfo h;
+    if (!zidx_validate(blob, len, &h))
+        return Z_DATA_ERROR;
+    U32 f = 0, c = 0, b = 0, l = 0;
+    if (!zidx_range(blob, &h, out_begin, out_len, &f, &c, &b, &l))
+        return Z_STREAM_ERROR;
+    if (first_piece)
+        *first_piece = f;
+    if (piece_count)
+        *piece_count = c;
+    if (piece_begin)
+        *piece_begin = b;
+    if (piece_len)
+        *piece_len = l;
+    return Z_OK;
+}
+
 extern "C" uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_plan *pl)
 {
     return pl ? pl->scratch_bytes : 0;
 }
 
 static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
-                                        U32 *dest_lens, I32 *statuses, I32 window_bits, int kind);
+                                        U32 *dest_lens, I32 *statuses, I32 window_bits, int kind,
+                                        const U8 *const *indexes = Z_NULL, const uint64_t *index_lens = Z_NULL);
 
 /* host-pointer batch: stage through one pair of device buffers */
 extern "C" ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources,
@@ -3059,8 +3422,18 @@ extern "C" ZlibReturn zsc_hip_uncompress_resync_batch(U32 count, const U8 *const
     return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 3);
 }
 
+extern "C" ZlibReturn zsc_hip_uncompress_indexed_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                                       U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                                       I32 window_bits, const U8 *const *indexes,
+                                                       const uint64_t *index_lens)
+{
+    return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 4, indexes,
+                                 index_lens);
+}
+
 static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
-                                        U32 *dest_lens, I32 *statuses, I32 window_bits, int kind)
+                                        U32 *dest_lens, I32 *statuses, I32 window_bits, int kind,
+                                        const U8 *const *indexes, const uint64_t *index_lens)
 {
     DeviceScope scope;
     ZSC_ASSERT(sources != Z_NULL);
@@ -3086,6 +3459,9 @@ static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32
                                                                      dof.data(), window_bits, 0)
                     : kind == 3 ? zsc_hip_inflate_plan_create_resync(&pl, count, source_lens, so.data(), dest_lens,
                                                                      dof.data(), window_bits)
+                    : kind == 4 ? zsc_hip_inflate_plan_create_indexed(&pl, count, source_lens, so.data(), dest_lens,
+                                                                      dof.data(), window_bits, indexes, index_lens,
+                                                                      Z_NULL, Z_NULL)
                                 : zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_lens,
                                                               dof.data(), window_bits);
     if (rc != Z_OK)
