@@ -147,6 +147,42 @@ I32 zsc_hip_deflate_plan_seg_schedule(const zsc_hip_deflate_plan *plan);
 
 void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *plan);
 
+/* The seek-point index, written with the stream (zsc_amd/csrc/deflate_index.h, DESIGN.md section 11;
+ * the blob is described under "seek-point indexes" below).  With the index enabled a run also works out,
+ * per stream, one seek point at the stream's start and one at the first block that holds input in every
+ * later chunk of chunk_bytes compressed bytes, how far each piece reads before its start, and the check
+ * value of each piece -- three launches per sub-batch after the bit packing.  An indexed inflate plan
+ * (zsc_hip_inflate_plan_create_indexed) decodes the stream from such a blob; no chunks plan is needed.
+ *
+ * Scope: plans made by zsc_hip_deflate_plan_create -- levels 1-9, every strategy, all three wrappers.
+ * Not covered: level 0 (zsc_hip_store_batch), the sections entry points (max_block_len < source_len)
+ * and the zsc_* one-shot functions, none of which hands out a plan.  A plan that never enables the
+ * index allocates, launches and returns exactly what it did without these functions.
+ *
+ * _index_enable: before _run.  chunk_bytes 0: the chunks plans' default, 128 KiB; values below 256 are
+ *   taken as 256.  Calling it again with another chunk_bytes re-sizes the storage (out_caps[i] /
+ *   chunk_bytes + 1 records of 32 bytes per buffer, 4 bytes per block slot of the largest sub-batch, 12
+ *   bytes per buffer; counted in zsc_hip_deflate_plan_scratch_bytes).
+ * _index_size, _index_export: valid after _results and before the next _run.  Z_STREAM_ERROR on a plan
+ *   that never enabled the index; Z_DATA_ERROR and 0 bytes for a buffer whose status is not Z_OK (a
+ *   short out_caps[i]); Z_BUF_ERROR, with *len the bytes needed -- what _index_size reports --, for a
+ *   short cap.  d_input is the device input the run read, UNCHANGED since the run: the windows of the
+ *   blob are gathered from it.  Given another input the blob is still well-formed but its windows are
+ *   wrong, and an indexed plan sends the stream to its serial decoder.  Nothing is read outside the
+ *   plan's buffers and bytes [in_offsets[buffer], + source_lens[buffer]) of d_input.
+ *   The blob's header: chunk_bytes as enabled; window_bits the value an inflate plan must be given
+ *   (the plan's own for zlib and raw streams, 16 + the window size for gzip); consumed the stream's
+ *   length; total source_lens[buffer].
+ * _index_ms: the summed device time of the three index launches over the sub-batches, averaged over
+ *   the runs since profiling was switched on like zsc_hip_deflate_plan_times (which they are not part
+ *   of: its whole-pass slot ends before the last sub-batch's index launches).  Valid after _results
+ *   while profiling is on. */
+ZlibReturn zsc_hip_deflate_plan_index_enable(zsc_hip_deflate_plan *plan, U32 chunk_bytes);
+ZlibReturn zsc_hip_deflate_plan_index_size(zsc_hip_deflate_plan *plan, U32 buffer, uint64_t *bytes);
+ZlibReturn zsc_hip_deflate_plan_index_export(zsc_hip_deflate_plan *plan, U32 buffer, const void *d_input,
+                                             U8 *blob, uint64_t cap, uint64_t *len);
+ZlibReturn zsc_hip_deflate_plan_index_ms(zsc_hip_deflate_plan *plan, float *ms);
+
 /* device-resident inflate batches ------------------------------------------ */
 
 /* Stream i occupies [src_offsets[i], +source_lens[i]) of the device input (offsets

@@ -14,6 +14,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
 * :func:`build_indexes`, :func:`uncompress_indexed_batch`, :func:`index_info`, :func:`index_range` --
   seek-point indexes: exported once from a chunks plan, then every later decode (or a range out of the
   middle) without the discovery;
+* :func:`compress_batch_indexed` -- streams written together with their seek-point indexes
+  (``DeflatePlan.index_enable`` / ``export_indexes``): no chunks plan is ever needed for them;
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -27,6 +29,6 @@ from .api import (  # noqa: F401
     compress, compress2, compress_gzip, uncompress, uncompress2, uncompress_gzip,
     compress_batch, compress_sections_batch, compress_sections_device, uncompress_batch, uncompress_sections_batch,
     uncompress_chunks_batch, uncompress_resync_batch, DeflatePlan, InflatePlan,
-    uncompress_indexed_batch, build_indexes, index_info, index_range,
+    uncompress_indexed_batch, build_indexes, index_info, index_range, compress_batch_indexed,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

@@ -124,6 +124,10 @@ def _load() -> C.CDLL:
     L.zsc_hip_deflate_plan_seg_schedule.restype = C.c_int32
     L.zsc_hip_deflate_plan_destroy.argtypes = [C.c_void_p]
     L.zsc_hip_deflate_plan_destroy.restype = None
+    L.zsc_hip_deflate_plan_index_enable.argtypes = [C.c_void_p, C.c_uint32]
+    L.zsc_hip_deflate_plan_index_size.argtypes = [C.c_void_p, C.c_uint32, u64p]
+    L.zsc_hip_deflate_plan_index_export.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint64, u64p]
+    L.zsc_hip_deflate_plan_index_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     return L
 
 
@@ -424,6 +428,30 @@ def build_indexes(sources: Sequence[bytes], dest_caps: Sequence[int], window_bit
         plan.close()
 
 
+def compress_batch_indexed(sources: Sequence[bytes], level: int = 6, window_bits: int = DEF_WBITS,
+                           mem_level: int = DEF_MEM_LEVEL, strategy: int = Z_DEFAULT_STRATEGY,
+                           chunk_bytes: int = 0) -> Tuple[List[bytes], List[int], List[Optional[bytes]]]:
+    """Every stream of compress_batch with its seek-point index, from one run of a DeflatePlan with
+    index_enable: (streams, statuses, blobs).  A blob goes to uncompress_indexed_batch or
+    InflatePlan(indexes=...) beside its stream; no chunks plan is needed to make it."""
+    import torch
+    plan = DeflatePlan([len(s) for s in sources], level, window_bits, mem_level, strategy)
+    try:
+        plan.index_enable(chunk_bytes)
+        src = torch.zeros(plan.in_bytes, dtype=torch.uint8, device="cuda")
+        dst = torch.empty(plan.out_bytes, dtype=torch.uint8, device="cuda")
+        for s, off in zip(sources, plan.in_offsets):
+            if s:
+                src[off:off + len(s)] = torch.frombuffer(bytearray(s), dtype=torch.uint8).cuda()
+        plan.run(src.data_ptr(), dst.data_ptr())
+        lens, stat = plan.results()
+        host = dst.cpu().numpy().tobytes()
+        streams = [host[off:off + n] if st == Z_OK else b"" for off, n, st in zip(plan.out_offsets, lens, stat)]
+        return streams, stat, plan.export_indexes(src.data_ptr())
+    finally:
+        plan.close()
+
+
 def _uncompress_batch(fn, sources, dest_caps, window_bits):
     count = len(sources)
     srcs = (C.c_char_p * count)(*sources)
@@ -643,6 +671,41 @@ class DeflatePlan:
         if rc != Z_OK:
             raise RuntimeError("profiling was not enabled before the run")
         return dict(zip(KERNEL_NAMES, list(t)))
+
+    def index_enable(self, chunk_bytes: int = 0) -> None:
+        """Before run(): every run also writes the seek-point index of every stream, one point per
+        chunk_bytes compressed bytes at the most (0: the library's default, 128 KiB)."""
+        rc = lib.zsc_hip_deflate_plan_index_enable(self._h, chunk_bytes)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_deflate_plan_index_enable failed: {rc}")
+
+    def export_indexes(self, d_input_ptr: int) -> List[Optional[bytes]]:
+        """After results() of a plan with index_enable: the blob of every buffer, None for a buffer whose
+        status is not Z_OK.  d_input_ptr is the device input the run read, unchanged since."""
+        out: List[Optional[bytes]] = []
+        for i in range(self.count):
+            need = C.c_uint64()
+            rc = lib.zsc_hip_deflate_plan_index_size(self._h, i, C.byref(need))
+            if rc == Z_DATA_ERROR:
+                out.append(None)
+                continue
+            if rc != Z_OK:
+                raise RuntimeError(f"zsc_hip_deflate_plan_index_size failed: {rc}")
+            buf = C.create_string_buffer(need.value)
+            got = C.c_uint64()
+            rc = lib.zsc_hip_deflate_plan_index_export(self._h, i, C.c_void_p(d_input_ptr), buf, need.value,
+                                                       C.byref(got))
+            if rc != Z_OK:
+                raise RuntimeError(f"zsc_hip_deflate_plan_index_export failed: {rc}")
+            out.append(buf.raw[:got.value])
+        return out
+
+    def index_ms(self) -> float:
+        """After results(), with profile() on: device time of the index launches per run, in milliseconds."""
+        ms = C.c_float()
+        if lib.zsc_hip_deflate_plan_index_ms(self._h, C.byref(ms)) != Z_OK:
+            raise RuntimeError("the index or profiling was not enabled before the run")
+        return ms.value
 
     def close(self) -> None:
         if self._h:

@@ -30,6 +30,7 @@
 #include "inflate_chunks.h"
 #include "inflate_resync.h"
 #include "inflate_index.h"
+#include "deflate_index.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "lz_parse_pipe.h"
@@ -588,6 +589,78 @@ __global__ __launch_bounds__(64) void k_emit(const uint8_t *__restrict__ in,
                (uint32_t *)(out + buf.out_off), &lds);
 }
 
+/* kernels 4c-4e (deflate_index.h): the seek-point index of every stream of a sub-batch, only for a plan
+ * with the index enabled.  4c: one wavefront per block */
+__global__ __launch_bounds__(64) void k_index_reach(const ZdBuf *__restrict__ bufs,
+                                                    const uint32_t *__restrict__ blk_owner,
+                                                    const uint32_t *__restrict__ syms,
+                                                    const ZdBlockRec *__restrict__ recs,
+                                                    const ZdParseOut *__restrict__ pout,
+                                                    const ZdBlockPlan *__restrict__ plans,
+                                                    uint32_t *__restrict__ reach, uint32_t nslots)
+{
+    const uint32_t slot = blockIdx.x;
+    if (slot >= nslots)
+        return;
+    const uint32_t b = blk_owner[slot];
+    const ZdBuf buf = bufs[b];
+    if (slot - buf.blk0 >= pout[b].nblocks || pout[b].nblocks > buf.max_blocks)
+        return;
+    const ZdBlockRec *rec = &recs[slot];
+    const uint32_t r = dix_block_reach(syms + buf.sym_off + rec->sym_begin, rec, &plans[slot]);
+    if (threadIdx.x == 0)
+        reach[slot] = r;
+}
+
+/* 4d: one thread per buffer, like k_layout; rec_off / npts: the sub-batch's first buffer */
+__global__ __launch_bounds__(64) void k_index_points(const ZdBuf *__restrict__ bufs,
+                                                     const ZdParseOut *__restrict__ pout,
+                                                     const ZdBlockRec *__restrict__ recs,
+                                                     const ZdBlockPlan *__restrict__ plans,
+                                                     const uint32_t *__restrict__ reach,
+                                                     const ZdResult *__restrict__ res, uint32_t chunk_bytes,
+                                                     ZidxRec *__restrict__ out,
+                                                     const uint64_t *__restrict__ rec_off,
+                                                     uint32_t *__restrict__ npts, uint32_t nbuf)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nbuf)
+        return;
+    dix_points(&bufs[b], &pout[b], recs + bufs[b].blk0, plans + bufs[b].blk0, reach + bufs[b].blk0, &res[b],
+               chunk_bytes, out + rec_off[b], (uint32_t)(rec_off[b + 1] - rec_off[b]), &npts[b]);
+}
+
+/* 4e: blockIdx.x = the buffer; the gridDim.y wavefronts of a buffer share its pieces */
+__global__ __launch_bounds__(64) void k_index_check(const uint8_t *__restrict__ in,
+                                                    const ZdBuf *__restrict__ bufs, ZidxRec *__restrict__ out,
+                                                    const uint64_t *__restrict__ rec_off,
+                                                    const uint32_t *__restrict__ npts, uint32_t nbuf)
+{
+    __shared__ CkLds lds;
+    const uint32_t b = blockIdx.x;
+    if (b >= nbuf)
+        return;
+    const uint32_t n = npts[b], wrap = bufs[b].wrap;
+    const uint8_t *src = in + bufs[b].in_off;
+    ZidxRec *recs = out + rec_off[b];
+    for (uint32_t p = blockIdx.y; p < n; p += gridDim.y) {
+        const uint32_t v = dix_piece_check(src, &recs[p], wrap, &lds);
+        if (threadIdx.x == 0)
+            recs[p].ck = v;
+        __syncthreads(); /* (one wave: orders the table's next rewrite after this piece's reads) */
+    }
+}
+
+/* the export's windows: piece i of one buffer copied from its input to its place in the gathered buffer */
+#define DIX_GATHER_THREADS 256
+__global__ __launch_bounds__(DIX_GATHER_THREADS) void k_index_gather(const uint8_t *__restrict__ in, uint32_t n,
+                                                                     const ZidxRec *__restrict__ recs,
+                                                                     uint8_t *__restrict__ out)
+{
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
+        dix_gather(in, &recs[i], out, threadIdx.x, DIX_GATHER_THREADS);
+}
+
 /* one stream of an inflate batch */
 typedef struct {
     uint64_t src_off, dst_off;
@@ -1110,6 +1183,22 @@ struct zsc_hip_deflate_plan {
     uint32_t profiled_runs = 0;
     hipStream_t last_stream = nullptr;
     uint64_t scratch_bytes = 0;
+    /* the seek-point index (deflate_index.h), off unless zsc_hip_deflate_plan_index_enable was called */
+    bool idx_on = false;
+    bool sectioned = false;       /* a plan of runs of sections: takes no index */
+    uint32_t idx_chunk = 0;       /* chunk_bytes of the blobs */
+    DevBuf d_idx_reach;           /* per block slot of a sub-batch: R_b (shared by the sub-batches) */
+    DevBuf d_idx_recs;            /* per buffer of the plan: out_cap / chunk_bytes + 1 records */
+    DevBuf d_idx_rec_off;         /* count + 1 first records (u64) */
+    DevBuf d_idx_npts;            /* per buffer: records written by the last run */
+    std::vector<uint64_t> idx_rec_off;
+    uint64_t idx_scratch = 0;     /* what of scratch_bytes the index holds */
+    bool idx_valid = false;       /* between _results and the next _run */
+    std::vector<ZdResult> idx_res;   /* the last run's results */
+    std::vector<uint32_t> idx_npts;  /* ... and point counts */
+    std::map<uint32_t, std::pair<std::vector<ZidxRec>, uint64_t>> idx_cache; /* records (woff set), window bytes */
+    std::vector<hipEvent_t> idx_events; /* 2 per sub-batch per profiled run */
+    size_t idx_events_used = 0;
 };
 
 namespace {
@@ -1225,6 +1314,20 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
                               const U32 *out_caps, I32 level, I32 window_bits, I32 mem_level,
                               ZlibStrategy strategy, const PlanRuns *runs);
 
+/* gives back what zsc_hip_deflate_plan_index_enable took (the caller has waited for the plan's work) */
+static void index_release(zsc_hip_deflate_plan *pl)
+{
+    pl->d_idx_reach.release();
+    pl->d_idx_recs.release();
+    pl->d_idx_rec_off.release();
+    pl->d_idx_npts.release();
+    pl->scratch_bytes -= pl->idx_scratch;
+    pl->idx_scratch = 0;
+    pl->idx_on = false;
+    pl->idx_valid = false;
+    pl->idx_cache.clear();
+}
+
 extern "C" ZlibReturn zsc_hip_deflate_plan_create(zsc_hip_deflate_plan **plan_out, U32 count,
                                                   const U32 *source_lens,
                                                   const uint64_t *in_offsets,
@@ -1262,6 +1365,7 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
     pl->wbits = wbits;
     pl->mem_level = mem_level;
     pl->strategy = (uint32_t)strategy;
+    pl->sectioned = runs != nullptr;
     pl->bufs.resize(count);
 
     /* input bytes per sub-batch; the scratch is ~14 B per input byte OF ONE SUB-BATCH.  Measured on
@@ -1474,7 +1578,37 @@ extern "C" void zsc_hip_deflate_plan_profile(zsc_hip_deflate_plan *plan, I32 ena
     ZSC_ASSERT(plan != Z_NULL);
     plan->profile = enable != 0;
     plan->events_used = 0; /* a new measurement window starts */
+    plan->idx_events_used = 0;
     plan->profiled_runs = 0;
+}
+
+/* the index of one sub-batch (deflate_index.h): reach per block, points per buffer, check value per piece */
+static void index_enqueue(zsc_hip_deflate_plan *pl, const SubBatch &sb, const uint8_t *in, hipStream_t st)
+{
+    const ZdBuf *bufs = (const ZdBuf *)sb.d_bufs.p;
+    uint32_t *reach = (uint32_t *)pl->d_idx_reach.p;
+    ZidxRec *out = (ZidxRec *)pl->d_idx_recs.p;
+    const uint64_t *rec_off = (const uint64_t *)pl->d_idx_rec_off.p + sb.first;
+    uint32_t *npts = (uint32_t *)pl->d_idx_npts.p + sb.first;
+    if (pl->profile)
+        (void)hipEventRecord(pl->idx_events[pl->idx_events_used++], st);
+    hipLaunchKernelGGL(k_index_reach, dim3(sb.nslots), dim3(64), 0, st, bufs, (const uint32_t *)sb.d_blk_owner.p,
+                       (const uint32_t *)pl->d_tmp_syms.p, (const ZdBlockRec *)pl->d_recs.p,
+                       (const ZdParseOut *)pl->d_pout.p, (const ZdBlockPlan *)pl->d_plans.p, reach, sb.nslots);
+    hipLaunchKernelGGL(k_index_points, dim3((sb.count + 63) / 64), dim3(64), 0, st, bufs,
+                       (const ZdParseOut *)pl->d_pout.p, (const ZdBlockRec *)pl->d_recs.p,
+                       (const ZdBlockPlan *)pl->d_plans.p, (const uint32_t *)reach,
+                       (const ZdResult *)pl->d_res.p + sb.first, pl->idx_chunk, out, rec_off, npts, sb.count);
+    /* enough wavefronts to fill the device where the buffers are few and long */
+    uint64_t most = 1;
+    for (uint32_t k = 0; k < sb.count; k++)
+        most = std::max(most, pl->idx_rec_off[sb.first + k + 1] - pl->idx_rec_off[sb.first + k]);
+    const uint64_t want = ((uint64_t)g_cus * 16u + sb.count - 1u) / sb.count;
+    const uint32_t per_buf = (uint32_t)std::min<uint64_t>(std::min(most, std::max<uint64_t>(want, 1)), 65535u);
+    hipLaunchKernelGGL(k_index_check, dim3(sb.count, per_buf), dim3(64), 0, st, in, bufs, out, rec_off,
+                       (const uint32_t *)npts, sb.count);
+    if (pl->profile)
+        (void)hipEventRecord(pl->idx_events[pl->idx_events_used++], st);
 }
 
 extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const void *d_input,
@@ -1503,6 +1637,16 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
             pl->events.push_back(e);
         }
         pl->profiled_runs++;
+    }
+    if (pl->idx_on) {
+        pl->idx_valid = false;
+        pl->idx_cache.clear();
+        if (pl->profile)
+            while (pl->idx_events.size() < pl->idx_events_used + pl->subs.size() * 2) {
+                hipEvent_t e;
+                HIP_TRY(hipEventCreate(&e), return Z_MEM_ERROR);
+                pl->idx_events.push_back(e);
+            }
     }
     auto mark = [&]() {
         if (pl->profile)
@@ -1612,6 +1756,8 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
                            (const ZdBlockRec *)recs, (const ZdParseOut *)pout,
                            (const ZdBlockPlan *)plans, out, sb.nslots);
         mark();
+        if (pl->idx_on) /* before the next sub-batch reuses recs, plans and tmp_syms */
+            index_enqueue(pl, sb, in, st);
     }
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
     return Z_OK;
@@ -1633,6 +1779,14 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_results(zsc_hip_deflate_plan *pl, U32
             dest_lens[i] = res[i].out_len;
         if (statuses)
             statuses[i] = res[i].status;
+    }
+    if (pl->idx_on && !pl->idx_valid) {
+        pl->idx_npts.assign(pl->count, 0u);
+        if (pl->count)
+            HIP_TRY(hipMemcpy(pl->idx_npts.data(), pl->d_idx_npts.p, 4ull * pl->count, hipMemcpyDeviceToHost),
+                    return Z_STREAM_ERROR);
+        pl->idx_res = res;
+        pl->idx_valid = true;
     }
     if (pl->profile && pl->profiled_runs) {
         /* mean per run over every run since profiling was switched on */
@@ -1712,9 +1866,160 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
     pl->d_plans.release();
     pl->d_pout.release();
     pl->d_res.release();
+    index_release(pl);
     for (hipEvent_t e : pl->events)
         (void)hipEventDestroy(e);
+    for (hipEvent_t e : pl->idx_events)
+        (void)hipEventDestroy(e);
     delete pl;
+}
+
+/* ---- the seek-point index of a deflate plan (deflate_index.h) ------------------------------- */
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_index_enable(zsc_hip_deflate_plan *pl, U32 chunk_bytes)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (pl->sectioned)
+        return Z_STREAM_ERROR;
+    static_assert(DIX_DEFAULT_CHUNK == CHK_DEFAULT_BYTES, "one default for both sides");
+    chunk_bytes = dix_chunk_bytes(chunk_bytes);
+    if (pl->idx_on && pl->idx_chunk == chunk_bytes)
+        return Z_OK;
+    (void)hipStreamSynchronize(pl->last_stream);
+    index_release(pl);
+    pl->idx_rec_off.assign((size_t)pl->count + 1u, 0);
+    uint64_t max_slots = 1;
+    for (uint32_t i = 0; i < pl->count; i++)
+        pl->idx_rec_off[i + 1u] = pl->idx_rec_off[i] + pl->bufs[i].out_cap / chunk_bytes + 1u;
+    for (const SubBatch &sb : pl->subs)
+        max_slots = std::max<uint64_t>(max_slots, sb.nslots);
+    const uint64_t nrec = pl->idx_rec_off[pl->count];
+    bool ok = pl->d_idx_reach.ensure(max_slots * 4u) && pl->d_idx_recs.ensure(std::max<uint64_t>(nrec, 1) * sizeof(ZidxRec)) &&
+              pl->d_idx_rec_off.ensure(((uint64_t)pl->count + 1u) * 8u) &&
+              pl->d_idx_npts.ensure(std::max(pl->count, 1u) * 4ull);
+    ok = ok && hipMemcpy(pl->d_idx_rec_off.p, pl->idx_rec_off.data(), ((size_t)pl->count + 1u) * 8u,
+                         hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemset(pl->d_idx_npts.p, 0, std::max(pl->count, 1u) * 4ull) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        index_release(pl);
+        return Z_MEM_ERROR;
+    }
+    pl->idx_scratch = pl->d_idx_reach.bytes + pl->d_idx_recs.bytes + pl->d_idx_rec_off.bytes + pl->d_idx_npts.bytes;
+    pl->scratch_bytes += pl->idx_scratch;
+    pl->idx_chunk = chunk_bytes;
+    pl->idx_on = true;
+    return Z_OK;
+}
+
+/* the records of `buffer` from the last run, woff set by a prefix sum of the window lengths (kept until the
+ * next run); Z_DATA_ERROR: the buffer has no stream, so no index */
+static ZlibReturn dix_records(zsc_hip_deflate_plan *pl, U32 buffer, const std::vector<ZidxRec> **recs,
+                              uint64_t *wbytes)
+{
+    if (!pl->idx_on || !pl->idx_valid || buffer >= pl->count)
+        return Z_STREAM_ERROR;
+    const uint32_t n = pl->idx_npts[buffer];
+    if (pl->idx_res[buffer].status != Z_OK || n == 0u)
+        return Z_DATA_ERROR;
+    auto hit = pl->idx_cache.find(buffer);
+    if (hit == pl->idx_cache.end()) {
+        if (n > pl->idx_rec_off[buffer + 1u] - pl->idx_rec_off[buffer])
+            return Z_STREAM_ERROR;
+        std::vector<ZidxRec> r(n);
+        HIP_TRY(hipMemcpy(r.data(), (const ZidxRec *)pl->d_idx_recs.p + pl->idx_rec_off[buffer], sizeof(ZidxRec) * n,
+                          hipMemcpyDeviceToHost),
+                return Z_STREAM_ERROR);
+        uint64_t total = 0;
+        for (ZidxRec &x : r) {
+            /* (the kernels' own output; checked all the same, so that the gather stays inside the input) */
+            if (x.wlen > ZIDX_WIN || x.wlen > x.off || (uint64_t)x.off + x.len > pl->bufs[buffer].in_len)
+                return Z_STREAM_ERROR;
+            x.woff = total;
+            total += x.wlen;
+        }
+        hit = pl->idx_cache.emplace(buffer, std::make_pair(std::move(r), total)).first;
+    }
+    *recs = &hit->second.first;
+    *wbytes = hit->second.second;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_index_size(zsc_hip_deflate_plan *pl, U32 buffer, uint64_t *bytes)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(bytes != Z_NULL);
+    *bytes = 0;
+    const std::vector<ZidxRec> *recs = nullptr;
+    uint64_t wbytes = 0;
+    const ZlibReturn rc = dix_records(pl, buffer, &recs, &wbytes);
+    if (rc == Z_OK)
+        *bytes = zidx_blob_bytes((uint32_t)recs->size(), wbytes);
+    return rc;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_index_export(zsc_hip_deflate_plan *pl, U32 buffer, const void *d_input,
+                                                        U8 *blob, uint64_t cap, uint64_t *len)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(len != Z_NULL);
+    *len = 0;
+    const std::vector<ZidxRec> *recs = nullptr;
+    uint64_t wbytes = 0;
+    const ZlibReturn rc = dix_records(pl, buffer, &recs, &wbytes);
+    if (rc != Z_OK)
+        return rc;
+    const uint32_t n = (uint32_t)recs->size();
+    const uint64_t bytes = zidx_blob_bytes(n, wbytes);
+    *len = bytes;
+    if (cap < bytes || blob == Z_NULL)
+        return Z_BUF_ERROR;
+    if (wbytes) {
+        if (d_input == Z_NULL)
+            return Z_STREAM_ERROR;
+        /* the windows, gathered from the input on the device, in one copy */
+        DevBuf d_recs, d_wins;
+        bool ok = d_recs.ensure(sizeof(ZidxRec) * n) && d_wins.ensure(wbytes) &&
+                  hipMemcpy(d_recs.p, recs->data(), sizeof(ZidxRec) * n, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) {
+            const uint32_t blocks = std::max(1u, std::min(n, (uint32_t)g_cus * 8u));
+            hipLaunchKernelGGL(k_index_gather, dim3(blocks), dim3(DIX_GATHER_THREADS), 0, pl->last_stream,
+                               (const uint8_t *)d_input + pl->bufs[buffer].in_off, n, (const ZidxRec *)d_recs.p,
+                               (uint8_t *)d_wins.p);
+            ok = hipStreamSynchronize(pl->last_stream) == hipSuccess &&
+                 hipMemcpy(blob + zidx_blob_bytes(n, 0), d_wins.p, wbytes, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        d_recs.release();
+        d_wins.release();
+        if (!ok)
+            return Z_MEM_ERROR;
+    }
+    const ZidxInfo h = dix_blob_info((uint32_t)pl->wrap, pl->wbits, pl->idx_chunk, pl->idx_res[buffer].out_len,
+                                     pl->bufs[buffer].in_len, n);
+    zidx_write_head(blob, &h, recs->data());
+    zidx_seal(blob, bytes);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_index_ms(zsc_hip_deflate_plan *pl, float *ms)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(ms != Z_NULL);
+    *ms = 0.f;
+    if (!pl->idx_on || !pl->profile || !pl->profiled_runs || !pl->idx_valid)
+        return Z_STREAM_ERROR;
+    float sum = 0.f;
+    for (size_t k = 0; k + 1 < pl->idx_events_used; k += 2) {
+        float t = 0.f;
+        (void)hipEventElapsedTime(&t, pl->idx_events[k], pl->idx_events[k + 1]);
+        sum += t;
+    }
+    *ms = sum / (float)pl->profiled_runs;
+    return Z_OK;
 }
 
 /* ---- level 0 --------------------------------------------------------------------- */
