@@ -183,6 +183,74 @@ ZlibReturn zsc_hip_deflate_plan_index_export(zsc_hip_deflate_plan *plan, U32 buf
                                              U8 *blob, uint64_t cap, uint64_t *len);
 ZlibReturn zsc_hip_deflate_plan_index_ms(zsc_hip_deflate_plan *plan, float *ms);
 
+/* Read-back verification: a plan's streams checked against their input on the device, where they lie
+ * (zsc_amd/csrc/deflate_verify.h).  With verification enabled a run keeps, for
+ * every block of every stream, where it starts and which input bytes it stands for; _verify then decodes
+ * every block from the emitted bits, one wave per block in one launch, and compares it with the input --
+ * a literal with its byte, a match as input[p + i] == input[p + i - dist] -- with no second output image;
+ * a second launch, one thread per buffer, checks that the blocks tile the input, the stream's header
+ * bytes, and the trailer as read from the stream against the blocks' own check values combined.  It guards
+ * against soft errors, a bad copy of the output to its resting place, and a bug in the Huffman plan,
+ * layout or emit kernels, none of whose results it reads.
+ *
+ * Scope: plans made by zsc_hip_deflate_plan_create -- levels 1-9, every strategy, window_bits 9-15, all
+ * three wrappers.  Not covered: level 0 (zsc_hip_store_batch), the sections entry points and the zsc_*
+ * one-shot functions.  A plan that never enables verification allocates, launches and returns exactly
+ * what it did without these functions.
+ *
+ * Storage, held from _verify_enable to destroy and counted in zsc_hip_deflate_plan_scratch_bytes: per
+ * block slot of the plan (source_lens[i] / ((1 << (mem_level + 6)) - 1) + 2 per buffer, all sub-batches)
+ * 16 bytes of block facts (zsc_hip_verify_block), 16 bytes of per-block verdict and check value and 4
+ * bytes naming its buffer; 52 bytes per buffer.
+ *
+ * The verdict of a buffer is that of its LOWEST-NUMBERED failing block (a later block may well fail too,
+ * e.g. one that copies from bytes the first one got wrong); header and trailer failures are reported
+ * only when no block failed.  Verification is stricter than a decoder where a decoder does not care:
+ * non-zero padding bits and a gzip header other than the plan's are failures.
+ *
+ * What an OK does not rest on: the symbol buffers, the Huffman plans, the plan's own check value of the
+ * input (the trailer is read from the stream, the value it must hold is computed anew per block).  What
+ * it does rest on: the kept block facts and the input, and -- the one dependence that remains -- for a
+ * RAW plan (window_bits < 0) the block compares alone, since a raw stream has no trailer to check.
+ *
+ * _verify_enable: before _run.  Z_STREAM_ERROR for a plan of sections.  The index may be enabled too.
+ * _verify: asynchronous on hip_stream; valid after _results and before the next _run, any number of
+ *   times; Z_STREAM_ERROR otherwise and on a plan that never enabled verification.  d_input is the input
+ *   the run read; d_output need not be the buffer the run wrote: a copy of it, with the plan's
+ *   out_offsets, is verified just the same -- this is how a caller checks the stream where it finally
+ *   rests.  Nothing is read outside [out_offsets[i], + out_caps[i]) (and the 64 readable bytes the layout
+ *   guarantees) and [in_offsets[i], + source_lens[i]), whatever the bits say: a block whose decode would
+ *   run past either fails with a reason.
+ * _verify_results: waits for the last _verify; one result per buffer.  ms (may be NULL): the device time
+ *   of that verification's launches, from HIP events on its stream.
+ * _verify_blocks: the kept block map of one buffer of the last run, in stream order.  Z_BUF_ERROR, with
+ *   *count the number needed, for a short cap; Z_DATA_ERROR and a count of 0 for a buffer whose status
+ *   is not Z_OK. */
+#define ZSC_HIP_VERIFY_OK          0
+#define ZSC_HIP_VERIFY_SKIPPED    -1  /* the buffer's status was not Z_OK: nothing to verify */
+#define ZSC_HIP_VERIFY_HEADER      1  /* stream header is not the plan's */
+#define ZSC_HIP_VERIFY_BLOCK_HDR   2  /* BFINAL / BTYPE / LEN / NLEN / padding */
+#define ZSC_HIP_VERIFY_CODES       3  /* dynamic header: invalid code set */
+#define ZSC_HIP_VERIFY_LITERAL     4  /* a literal or stored byte differs from the input */
+#define ZSC_HIP_VERIFY_DISTANCE    5  /* distance 0, before the input's start, or beyond the window */
+#define ZSC_HIP_VERIFY_MATCH       6  /* the bytes a match copies are not the input's */
+#define ZSC_HIP_VERIFY_LENGTH      7  /* the block passes or misses its input end, or an invalid symbol */
+#define ZSC_HIP_VERIFY_BIT_END     8  /* the block does not end at the next block's first bit / the trailer */
+#define ZSC_HIP_VERIFY_TRAILER     9  /* check value or ISIZE */
+
+typedef struct { I32 verdict; U32 block; U32 bit_off; U32 in_pos; } zsc_hip_verify_result;
+/* block: the failing block in stream order, 0xFFFFFFFF for OK / SKIPPED / HEADER / TRAILER;
+ * bit_off: the block's first bit; in_pos: the input offset the check had reached */
+typedef struct { U32 bit_off, in_begin, in_len, type_last; } zsc_hip_verify_block; /* type | last << 8 */
+
+ZlibReturn zsc_hip_deflate_plan_verify_enable(zsc_hip_deflate_plan *plan);
+ZlibReturn zsc_hip_deflate_plan_verify(zsc_hip_deflate_plan *plan, const void *d_input,
+                                       const void *d_output, void *hip_stream);
+ZlibReturn zsc_hip_deflate_plan_verify_results(zsc_hip_deflate_plan *plan,
+                                               zsc_hip_verify_result *results, float *ms);
+ZlibReturn zsc_hip_deflate_plan_verify_blocks(zsc_hip_deflate_plan *plan, U32 buffer,
+                                              zsc_hip_verify_block *blocks, U32 cap, U32 *count);
+
 /* device-resident inflate batches ------------------------------------------ */
 
 /* Stream i occupies [src_offsets[i], +source_lens[i]) of the device input (offsets

@@ -16,6 +16,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
   middle) without the discovery;
 * :func:`compress_batch_indexed` -- streams written together with their seek-point indexes
   (``DeflatePlan.index_enable`` / ``export_indexes``): no chunks plan is ever needed for them;
+* :func:`compress_batch_verified` -- streams checked against their input on the device, block by block,
+  before they leave it (``DeflatePlan.verify_enable`` / ``verify`` / ``verify_results``);
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -30,5 +32,7 @@ from .api import (  # noqa: F401
     compress_batch, compress_sections_batch, compress_sections_device, uncompress_batch, uncompress_sections_batch,
     uncompress_chunks_batch, uncompress_resync_batch, DeflatePlan, InflatePlan,
     uncompress_indexed_batch, build_indexes, index_info, index_range, compress_batch_indexed,
+    compress_batch_verified, VERIFY_OK, VERIFY_SKIPPED, VERIFY_HEADER, VERIFY_BLOCK_HDR, VERIFY_CODES, VERIFY_LITERAL,
+    VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH, VERIFY_BIT_END, VERIFY_TRAILER,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

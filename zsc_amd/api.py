@@ -38,6 +38,22 @@ class IndexHeader(C.Structure):
                 ("total_out", C.c_uint32), ("trailer_offset", C.c_uint32), ("points", C.c_uint32)]
 
 
+class VerifyResult(C.Structure):
+    """zsc_hip_verify_result (include/zsc_hip.h)"""
+    _fields_ = [("verdict", C.c_int32), ("block", C.c_uint32), ("bit_off", C.c_uint32), ("in_pos", C.c_uint32)]
+
+
+class VerifyBlock(C.Structure):
+    """zsc_hip_verify_block (include/zsc_hip.h)"""
+    _fields_ = [("bit_off", C.c_uint32), ("in_begin", C.c_uint32), ("in_len", C.c_uint32), ("type_last", C.c_uint32)]
+
+
+# ZSC_HIP_VERIFY_*: the verdict of verifying one buffer's stream against its input
+VERIFY_OK, VERIFY_SKIPPED = 0, -1
+(VERIFY_HEADER, VERIFY_BLOCK_HDR, VERIFY_CODES, VERIFY_LITERAL, VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH,
+ VERIFY_BIT_END, VERIFY_TRAILER) = range(1, 10)
+
+
 def _load() -> C.CDLL:
     # PyTorch-ROCm wheels bundle their own libamdhip64 (SONAME libamdhip64.so.7, the same
     # as /opt/rocm's).  Two HIP runtimes in one process cannot both own the GPU, so when
@@ -128,6 +144,10 @@ def _load() -> C.CDLL:
     L.zsc_hip_deflate_plan_index_size.argtypes = [C.c_void_p, C.c_uint32, u64p]
     L.zsc_hip_deflate_plan_index_export.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint64, u64p]
     L.zsc_hip_deflate_plan_index_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.zsc_hip_deflate_plan_verify_enable.argtypes = [C.c_void_p]
+    L.zsc_hip_deflate_plan_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.zsc_hip_deflate_plan_verify_results.argtypes = [C.c_void_p, C.POINTER(VerifyResult), C.POINTER(C.c_float)]
+    L.zsc_hip_deflate_plan_verify_blocks.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(VerifyBlock), C.c_uint32, u32p]
     return L
 
 
@@ -452,6 +472,36 @@ def compress_batch_indexed(sources: Sequence[bytes], level: int = 6, window_bits
         plan.close()
 
 
+def compress_batch_verified(sources: Sequence[bytes], level: int = 6, window_bits: int = DEF_WBITS,
+                            mem_level: int = DEF_MEM_LEVEL, strategy: int = Z_DEFAULT_STRATEGY
+                            ) -> Tuple[int, List[bytes], List[int], List[dict]]:
+    """compress_batch with every stream verified against its input on the device before it is copied to the
+    host, from one run of a DeflatePlan with verify_enable: (rc, streams, statuses, verdicts).  verdicts are
+    DeflatePlan.verify_results(); rc is Z_OK when the batch ran and no stream failed its verification,
+    Z_DATA_ERROR when one did (its bytes are returned all the same)."""
+    import torch
+    plan = DeflatePlan([len(s) for s in sources], level, window_bits, mem_level, strategy)
+    try:
+        plan.verify_enable()
+        src = torch.zeros(plan.in_bytes, dtype=torch.uint8, device="cuda")
+        dst = torch.empty(plan.out_bytes, dtype=torch.uint8, device="cuda")
+        for s, off in zip(sources, plan.in_offsets):
+            if s:
+                src[off:off + len(s)] = torch.frombuffer(bytearray(s), dtype=torch.uint8).cuda()
+        plan.run(src.data_ptr(), dst.data_ptr())
+        lens, stat = plan.results()
+        rc = plan.verify(src.data_ptr(), dst.data_ptr())
+        if rc != Z_OK:
+            return rc, [], stat, []
+        verdicts = plan.verify_results()
+        host = dst.cpu().numpy().tobytes()
+        streams = [host[off:off + n] if st == Z_OK else b"" for off, n, st in zip(plan.out_offsets, lens, stat)]
+        bad = any(v["verdict"] not in (VERIFY_OK, VERIFY_SKIPPED) for v in verdicts)
+        return (Z_DATA_ERROR if bad else Z_OK), streams, stat, verdicts
+    finally:
+        plan.close()
+
+
 def _uncompress_batch(fn, sources, dest_caps, window_bits):
     count = len(sources)
     srcs = (C.c_char_p * count)(*sources)
@@ -706,6 +756,53 @@ class DeflatePlan:
         if lib.zsc_hip_deflate_plan_index_ms(self._h, C.byref(ms)) != Z_OK:
             raise RuntimeError("the index or profiling was not enabled before the run")
         return ms.value
+
+    def verify_enable(self) -> None:
+        """Before run(): every run also keeps where each block of each stream starts and which input bytes
+        it stands for, so that verify() can check the streams against the input on the device."""
+        rc = lib.zsc_hip_deflate_plan_verify_enable(self._h)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_deflate_plan_verify_enable failed: {rc}")
+
+    def verify(self, d_input: int, d_output: int, stream: int = 0) -> int:
+        """After results(), any number of times: enqueue the verification of the streams at d_output (the
+        run's output or a copy of it, with the plan's out_offsets) against the input at d_input.  Returns
+        the ZlibReturn: Z_STREAM_ERROR on a plan without verify_enable()."""
+        return lib.zsc_hip_deflate_plan_verify(self._h, C.c_void_p(d_input), C.c_void_p(d_output), C.c_void_p(stream))
+
+    def verify_results(self) -> List[dict]:
+        """Waits for the last verify(): per buffer {"verdict", "block", "bit_off", "in_pos"} -- verdict one of
+        VERIFY_*, block the lowest-numbered failing block (0xFFFFFFFF where the verdict names none)."""
+        res = (VerifyResult * max(self.count, 1))()
+        ms = C.c_float()
+        rc = lib.zsc_hip_deflate_plan_verify_results(self._h, res, C.byref(ms))
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_deflate_plan_verify_results failed: {rc}")
+        self._verify_ms = ms.value
+        return [{"verdict": r.verdict, "block": r.block, "bit_off": r.bit_off, "in_pos": r.in_pos}
+                for r in res[:self.count]]
+
+    def verify_ms(self) -> float:
+        """After verify_results(): device time of that verification's launches, in milliseconds."""
+        if getattr(self, "_verify_ms", None) is None:
+            raise RuntimeError("no verify_results() yet")
+        return self._verify_ms
+
+    def verify_blocks(self, i: int) -> List[Tuple[int, int, int, int, int]]:
+        """After results() of a plan with verify_enable(): the block map of buffer i, in stream order:
+        (bit_off, in_begin, in_len, type, last) -- type 0 stored, 1 static, 2 dynamic.  [] for a buffer whose
+        status is not Z_OK."""
+        n = C.c_uint32()
+        rc = lib.zsc_hip_deflate_plan_verify_blocks(self._h, i, None, 0, C.byref(n))
+        if rc == Z_DATA_ERROR:
+            return []
+        if rc not in (Z_OK, Z_BUF_ERROR):
+            raise RuntimeError(f"zsc_hip_deflate_plan_verify_blocks failed: {rc}")
+        blocks = (VerifyBlock * max(n.value, 1))()
+        rc = lib.zsc_hip_deflate_plan_verify_blocks(self._h, i, blocks, n.value, C.byref(n))
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_deflate_plan_verify_blocks failed: {rc}")
+        return [(b.bit_off, b.in_begin, b.in_len, b.type_last & 0xff, b.type_last >> 8) for b in blocks[:n.value]]
 
     def close(self) -> None:
         if self._h:

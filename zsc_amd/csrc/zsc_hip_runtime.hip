@@ -31,6 +31,7 @@
 #include "inflate_resync.h"
 #include "inflate_index.h"
 #include "deflate_index.h"
+#include "deflate_verify.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "lz_parse_pipe.h"
@@ -661,6 +662,68 @@ __global__ __launch_bounds__(DIX_GATHER_THREADS) void k_index_gather(const uint8
         dix_gather(in, &recs[i], out, threadIdx.x, DIX_GATHER_THREADS);
 }
 
+/* kernels 4f-4h (deflate_verify.h): read-back verification, only for a plan with verification enabled.
+ * 4f, per sub-batch: one thread per block slot keeps the block's facts; first / nblk: the sub-batch's
+ * first buffer */
+__global__ __launch_bounds__(256) void k_verify_keep(const ZdBuf *__restrict__ bufs,
+                                                     const uint32_t *__restrict__ blk_owner,
+                                                     const ZdParseOut *__restrict__ pout,
+                                                     const ZdBlockRec *__restrict__ recs,
+                                                     const ZdBlockPlan *__restrict__ plans,
+                                                     const ZdResult *__restrict__ res,
+                                                     const DvfBuf *__restrict__ vbufs, DvfBlock *__restrict__ facts,
+                                                     uint32_t *__restrict__ nblk, uint32_t nslots)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= nslots)
+        return;
+    const uint32_t b = blk_owner[slot];
+    const uint32_t blk0 = bufs[b].blk0;
+    dvf_keep(&bufs[b], &pout[b], recs + blk0, plans + blk0, &res[b], slot - blk0, facts + vbufs[b].first, &nblk[b]);
+}
+
+/* 4g, on request: one wavefront per kept block of the whole plan */
+__global__ __launch_bounds__(64) void k_verify_blocks(const uint8_t *__restrict__ in,
+                                                      const uint8_t *__restrict__ out,
+                                                      const DvfBuf *__restrict__ vbufs,
+                                                      const uint32_t *__restrict__ owner,
+                                                      const DvfBlock *__restrict__ facts,
+                                                      const uint32_t *__restrict__ nblk,
+                                                      const ZdResult *__restrict__ res,
+                                                      DvfVerdict *__restrict__ verd, uint32_t wrap, uint32_t wbits,
+                                                      uint32_t nslots)
+{
+    __shared__ DvfLds lds;
+    const uint32_t slot = blockIdx.x;
+    if (slot >= nslots)
+        return;
+    const uint32_t b = owner[slot];
+    const DvfBuf buf = vbufs[b];
+    const uint32_t n = nblk[b], j = slot - buf.first;
+    if (j >= n || n > buf.max_blocks)
+        return;
+    dvf_block_item(in + buf.in_off, out + buf.out_off, &buf, facts + buf.first, n, j, res[b].out_len, wrap, wbits,
+                   &lds, verd + buf.first);
+}
+
+/* 4h: one thread per buffer */
+__global__ __launch_bounds__(64) void k_verify_finish(const uint8_t *__restrict__ out,
+                                                      const DvfBuf *__restrict__ vbufs,
+                                                      const DvfBlock *__restrict__ facts,
+                                                      const DvfVerdict *__restrict__ verd,
+                                                      const uint32_t *__restrict__ nblk,
+                                                      const ZdResult *__restrict__ res, uint32_t wrap,
+                                                      uint32_t wbits, uint32_t level, uint32_t strategy,
+                                                      DvfResult *__restrict__ results, uint32_t nbuf)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nbuf)
+        return;
+    const uint32_t n = nblk[b] <= vbufs[b].max_blocks ? nblk[b] : 0u;
+    dvf_finish(out + vbufs[b].out_off, &vbufs[b], facts + vbufs[b].first, verd + vbufs[b].first, n, &res[b], wrap,
+               wbits, level, strategy, &results[b]);
+}
+
 /* one stream of an inflate batch */
 typedef struct {
     uint64_t src_off, dst_off;
@@ -1199,6 +1262,22 @@ struct zsc_hip_deflate_plan {
     std::map<uint32_t, std::pair<std::vector<ZidxRec>, uint64_t>> idx_cache; /* records (woff set), window bytes */
     std::vector<hipEvent_t> idx_events; /* 2 per sub-batch per profiled run */
     size_t idx_events_used = 0;
+    /* read-back verification (deflate_verify.h), off unless zsc_hip_deflate_plan_verify_enable was called */
+    bool vf_on = false;
+    bool vf_valid = false;        /* between _results and the next _run */
+    bool vf_ran = false;          /* a _verify since then */
+    uint32_t vf_slots = 0;        /* block slots of the whole plan */
+    DevBuf d_vf_bufs;             /* DvfBuf per buffer */
+    DevBuf d_vf_owner;            /* per block slot: its buffer */
+    DevBuf d_vf_facts;            /* per block slot: DvfBlock, kept by every run */
+    DevBuf d_vf_verd;             /* per block slot: DvfVerdict of the last _verify */
+    DevBuf d_vf_nblk;             /* per buffer: blocks kept by the last run */
+    DevBuf d_vf_res;              /* per buffer: DvfResult of the last _verify */
+    std::vector<DvfBuf> vf_bufs;
+    std::vector<ZdResult> vf_run_res; /* the last run's results */
+    uint64_t vf_scratch = 0;      /* what of scratch_bytes verification holds */
+    hipEvent_t vf_ev[2] = {nullptr, nullptr};
+    hipStream_t vf_stream = nullptr;
 };
 
 namespace {
@@ -1326,6 +1405,27 @@ static void index_release(zsc_hip_deflate_plan *pl)
     pl->idx_on = false;
     pl->idx_valid = false;
     pl->idx_cache.clear();
+}
+
+/* the same for zsc_hip_deflate_plan_verify_enable */
+static void verify_release(zsc_hip_deflate_plan *pl)
+{
+    pl->d_vf_bufs.release();
+    pl->d_vf_owner.release();
+    pl->d_vf_facts.release();
+    pl->d_vf_verd.release();
+    pl->d_vf_nblk.release();
+    pl->d_vf_res.release();
+    pl->scratch_bytes -= pl->vf_scratch;
+    pl->vf_scratch = 0;
+    pl->vf_on = false;
+    pl->vf_valid = false;
+    pl->vf_ran = false;
+    for (hipEvent_t &e : pl->vf_ev) {
+        if (e)
+            (void)hipEventDestroy(e);
+        e = nullptr;
+    }
 }
 
 extern "C" ZlibReturn zsc_hip_deflate_plan_create(zsc_hip_deflate_plan **plan_out, U32 count,
@@ -1638,6 +1738,10 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
         }
         pl->profiled_runs++;
     }
+    if (pl->vf_on) {
+        pl->vf_valid = false;
+        pl->vf_ran = false;
+    }
     if (pl->idx_on) {
         pl->idx_valid = false;
         pl->idx_cache.clear();
@@ -1758,6 +1862,12 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
         mark();
         if (pl->idx_on) /* before the next sub-batch reuses recs, plans and tmp_syms */
             index_enqueue(pl, sb, in, st);
+        if (pl->vf_on) /* the same: the block facts of this sub-batch, out of recs and plans */
+            hipLaunchKernelGGL(k_verify_keep, dim3((sb.nslots + 255) / 256), dim3(256), 0, st, bufs,
+                               (const uint32_t *)sb.d_blk_owner.p, (const ZdParseOut *)pout, (const ZdBlockRec *)recs,
+                               (const ZdBlockPlan *)plans, (const ZdResult *)res,
+                               (const DvfBuf *)pl->d_vf_bufs.p + sb.first, (DvfBlock *)pl->d_vf_facts.p,
+                               (uint32_t *)pl->d_vf_nblk.p + sb.first, sb.nslots);
     }
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
     return Z_OK;
@@ -1779,6 +1889,10 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_results(zsc_hip_deflate_plan *pl, U32
             dest_lens[i] = res[i].out_len;
         if (statuses)
             statuses[i] = res[i].status;
+    }
+    if (pl->vf_on && !pl->vf_valid) {
+        pl->vf_run_res = res;
+        pl->vf_valid = true;
     }
     if (pl->idx_on && !pl->idx_valid) {
         pl->idx_npts.assign(pl->count, 0u);
@@ -1867,6 +1981,7 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
     pl->d_pout.release();
     pl->d_res.release();
     index_release(pl);
+    verify_release(pl);
     for (hipEvent_t e : pl->events)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : pl->idx_events)
@@ -2019,6 +2134,139 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_index_ms(zsc_hip_deflate_plan *pl, fl
         sum += t;
     }
     *ms = sum / (float)pl->profiled_runs;
+    return Z_OK;
+}
+
+/* ---- read-back verification of a deflate plan (deflate_verify.h) ---------------------------- */
+
+static_assert(ZSC_HIP_VERIFY_OK == DVF_OK && ZSC_HIP_VERIFY_SKIPPED == DVF_SKIPPED && ZSC_HIP_VERIFY_HEADER == DVF_HEADER &&
+                  ZSC_HIP_VERIFY_BLOCK_HDR == DVF_BLOCK_HDR && ZSC_HIP_VERIFY_CODES == DVF_CODES &&
+                  ZSC_HIP_VERIFY_LITERAL == DVF_LITERAL && ZSC_HIP_VERIFY_DISTANCE == DVF_DISTANCE &&
+                  ZSC_HIP_VERIFY_MATCH == DVF_MATCH && ZSC_HIP_VERIFY_LENGTH == DVF_LENGTH &&
+                  ZSC_HIP_VERIFY_BIT_END == DVF_BIT_END && ZSC_HIP_VERIFY_TRAILER == DVF_TRAILER,
+              "the kernels' verdicts are the header's");
+static_assert(sizeof(zsc_hip_verify_result) == sizeof(DvfResult) && sizeof(zsc_hip_verify_block) == sizeof(DvfBlock),
+              "copied out as they are");
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_verify_enable(zsc_hip_deflate_plan *pl)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (pl->sectioned)
+        return Z_STREAM_ERROR;
+    if (pl->vf_on)
+        return Z_OK;
+    (void)hipStreamSynchronize(pl->last_stream);
+    uint64_t slots = 0;
+    pl->vf_bufs.assign(pl->count, DvfBuf());
+    for (uint32_t i = 0; i < pl->count; i++) {
+        const ZdBuf &b = pl->bufs[i];
+        DvfBuf &v = pl->vf_bufs[i];
+        v.in_off = b.in_off;
+        v.out_off = b.out_off;
+        v.in_len = b.in_len;
+        v.out_cap = b.out_cap;
+        v.first = (uint32_t)slots;
+        v.max_blocks = b.max_blocks;
+        slots += b.max_blocks;
+        if (slots >= 0x7fffffffull) /* one launch takes a wavefront per slot */
+            return Z_MEM_ERROR;
+    }
+    std::vector<uint32_t> owner((size_t)slots);
+    for (uint32_t i = 0; i < pl->count; i++)
+        std::fill(owner.begin() + pl->vf_bufs[i].first, owner.begin() + pl->vf_bufs[i].first + pl->vf_bufs[i].max_blocks, i);
+    const uint64_t nb = std::max(pl->count, 1u), ns = std::max<uint64_t>(slots, 1);
+    bool ok = pl->d_vf_bufs.ensure(nb * sizeof(DvfBuf)) && pl->d_vf_owner.ensure(ns * 4u) &&
+              pl->d_vf_facts.ensure(ns * sizeof(DvfBlock)) && pl->d_vf_verd.ensure(ns * sizeof(DvfVerdict)) &&
+              pl->d_vf_nblk.ensure(nb * 4u) && pl->d_vf_res.ensure(nb * sizeof(DvfResult));
+    ok = ok && hipMemcpy(pl->d_vf_bufs.p, pl->vf_bufs.data(), sizeof(DvfBuf) * pl->count, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(pl->d_vf_owner.p, owner.data(), 4ull * slots, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemset(pl->d_vf_nblk.p, 0, nb * 4u) == hipSuccess && hipEventCreate(&pl->vf_ev[0]) == hipSuccess &&
+         hipEventCreate(&pl->vf_ev[1]) == hipSuccess;
+    pl->vf_scratch = pl->d_vf_bufs.bytes + pl->d_vf_owner.bytes + pl->d_vf_facts.bytes + pl->d_vf_verd.bytes +
+                     pl->d_vf_nblk.bytes + pl->d_vf_res.bytes;
+    pl->scratch_bytes += pl->vf_scratch;
+    if (!ok) {
+        (void)hipGetLastError();
+        verify_release(pl);
+        return Z_MEM_ERROR;
+    }
+    pl->vf_slots = (uint32_t)slots;
+    pl->vf_on = true;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_verify(zsc_hip_deflate_plan *pl, const void *d_input, const void *d_output,
+                                                  void *hip_stream)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (!pl->vf_on || !pl->vf_valid || (pl->count != 0 && (d_input == Z_NULL || d_output == Z_NULL)))
+        return Z_STREAM_ERROR;
+    hipStream_t st = (hipStream_t)hip_stream;
+    (void)hipGetLastError();
+    if (pl->vf_ran && pl->vf_stream != st) /* the verdicts of the one before are still being written */
+        HIP_TRY(hipStreamSynchronize(pl->vf_stream), return Z_STREAM_ERROR);
+    pl->vf_stream = st;
+    pl->vf_ran = true;
+    (void)hipEventRecord(pl->vf_ev[0], st);
+    if (pl->vf_slots)
+        hipLaunchKernelGGL(k_verify_blocks, dim3(pl->vf_slots), dim3(64), 0, st, (const uint8_t *)d_input,
+                           (const uint8_t *)d_output, (const DvfBuf *)pl->d_vf_bufs.p,
+                           (const uint32_t *)pl->d_vf_owner.p, (const DvfBlock *)pl->d_vf_facts.p,
+                           (const uint32_t *)pl->d_vf_nblk.p, (const ZdResult *)pl->d_res.p,
+                           (DvfVerdict *)pl->d_vf_verd.p, (uint32_t)pl->wrap, (uint32_t)pl->wbits, pl->vf_slots);
+    if (pl->count)
+        hipLaunchKernelGGL(k_verify_finish, dim3((pl->count + 63) / 64), dim3(64), 0, st, (const uint8_t *)d_output,
+                           (const DvfBuf *)pl->d_vf_bufs.p, (const DvfBlock *)pl->d_vf_facts.p,
+                           (const DvfVerdict *)pl->d_vf_verd.p, (const uint32_t *)pl->d_vf_nblk.p,
+                           (const ZdResult *)pl->d_res.p, (uint32_t)pl->wrap, (uint32_t)pl->wbits, (uint32_t)pl->level,
+                           pl->strategy, (DvfResult *)pl->d_vf_res.p, pl->count);
+    (void)hipEventRecord(pl->vf_ev[1], st);
+    HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_verify_results(zsc_hip_deflate_plan *pl, zsc_hip_verify_result *results,
+                                                          float *ms)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (ms)
+        *ms = 0.f;
+    if (!pl->vf_on || !pl->vf_valid || !pl->vf_ran)
+        return Z_STREAM_ERROR;
+    HIP_TRY(hipStreamSynchronize(pl->vf_stream), return Z_STREAM_ERROR);
+    if (pl->count && results)
+        HIP_TRY(hipMemcpy(results, pl->d_vf_res.p, sizeof(DvfResult) * pl->count, hipMemcpyDeviceToHost),
+                return Z_STREAM_ERROR);
+    if (ms)
+        (void)hipEventElapsedTime(ms, pl->vf_ev[0], pl->vf_ev[1]);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_verify_blocks(zsc_hip_deflate_plan *pl, U32 buffer,
+                                                         zsc_hip_verify_block *blocks, U32 cap, U32 *count)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(count != Z_NULL);
+    *count = 0;
+    if (!pl->vf_on || !pl->vf_valid || buffer >= pl->count)
+        return Z_STREAM_ERROR;
+    if (pl->vf_run_res[buffer].status != Z_OK)
+        return Z_DATA_ERROR;
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, (const uint32_t *)pl->d_vf_nblk.p + buffer, 4, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    if (n > pl->vf_bufs[buffer].max_blocks)
+        return Z_STREAM_ERROR;
+    *count = n;
+    if (cap < n || (n != 0 && blocks == Z_NULL))
+        return Z_BUF_ERROR;
+    if (n)
+        HIP_TRY(hipMemcpy(blocks, (const DvfBlock *)pl->d_vf_facts.p + pl->vf_bufs[buffer].first, sizeof(DvfBlock) * n,
+                          hipMemcpyDeviceToHost),
+                return Z_STREAM_ERROR);
     return Z_OK;
 }
 
