@@ -28,8 +28,11 @@
  * "hash sort staged wholly in LDS"): 41 ms per 1024 Canterbury-like sets with the ballot
  * multi-split, 49 ms with an LDS match table in its place, against 40 ms for this version --
  * the scattered accesses move from the texture path to LDS bank conflicts and cost the same
- * ~10 CU cycles per position.  At 145 G key-passes/s the sort already runs at the rate of
- * published one-sweep radix sorts; it stays as it was.
+ * ~10 CU cycles per position.  Neither HBM (about 3 TB/s read and written) nor instruction issue
+ * (about 100 instructions per 64 positions) nor the LDS explains that rate; what the scatter loops
+ * did was to keep one step of 64 positions in flight per wave, each step waiting for the scattered
+ * stores of the one before it.  A wave now takes HS_SCATTER_BATCH steps through a scatter as one
+ * unit (hs_scatter_batch; hs_directory likewise), DESIGN section 5g.
  *
  * Bytes per input byte (TILE positions): read 2 (input, twice) + tmp 4w+4r +
  * sorted 4w(+4r for dir) + rank 2w + dir 2w.
@@ -63,20 +66,24 @@ typedef struct {
 } HsTile;
 
 /* UPDATE_HASH over three bytes, reference src/deflate.c:174-175 */
+DEV uint32_t hs_hash_word(uint32_t w) /* of the three low bytes of w, the first one lowest */
+{
+    const uint32_t b0 = w & 0xff, b1 = (w >> 8) & 0xff, b2 = (w >> 16) & 0xff;
+    return ((b0 << 10) ^ (b1 << 5) ^ b2) & ZD_HASH_MASK;
+}
+
+/* the three bytes at pos in the three low bytes of a word (the top byte is whatever follows them, or 0):
+ * on the usual path nothing but the load, so that a caller can have several of them in flight */
+DEV uint32_t hs_word3(const uint8_t *in, uint32_t pos, uint32_t n)
+{
+    if (pos + 4 <= n)
+        return ld_u32(in + pos);
+    return (uint32_t)in[pos] | ((uint32_t)in[pos + 1] << 8) | ((uint32_t)in[pos + 2] << 16);
+}
+
 DEV uint32_t hs_hash3(const uint8_t *in, uint32_t pos, uint32_t n)
 {
-    uint32_t b0, b1, b2;
-    if (pos + 4 <= n) {
-        uint32_t w = ld_u32(in + pos);
-        b0 = w & 0xff;
-        b1 = (w >> 8) & 0xff;
-        b2 = (w >> 16) & 0xff;
-    } else {
-        b0 = in[pos];
-        b1 = in[pos + 1];
-        b2 = in[pos + 2];
-    }
-    return ((b0 << 10) ^ (b1 << 5) ^ b2) & ZD_HASH_MASK;
+    return hs_hash_word(hs_word3(in, pos, n));
 }
 
 DEV uint32_t hs_slice(uint32_t m)
@@ -85,76 +92,111 @@ DEV uint32_t hs_slice(uint32_t m)
     return per * WAVE;
 }
 
-/* stable scatter of one pass; key_of_tmp selects pass 2 (source = tmp) */
-DEV void hs_scatter(const HsTile &t, HsLds *lds, int w, int pass)
+/* Steps (of WAVE positions) a wave takes through a scatter as one unit: all their loads, then their
+ * multi-splits in step order, then all their stores.  A gfx9 wave counts loads and stores with one
+ * counter that retires in order, so the wait for a step's load is also a wait for every scattered
+ * store issued before it; a wave that loops over single steps has one store round trip per step on its
+ * critical path, a batch has one per HS_SCATTER_BATCH steps. */
+#define HS_SCATTER_BATCH 4
+
+/* One batch of a wave's scatter: the steps at s, s + WAVE, ... of its positions [lo, end).  FULL: every
+ * lane of every step has a position (all but a wave's last batch) -- one piece of straight-line code, in
+ * which the compiler keeps the loads, and then the stores, in flight together; where lanes have to be
+ * switched off step by step it cuts the code into pieces that each wait for the memory operations before. */
+template <bool FULL>
+DEV void hs_scatter_batch(const HsTile &t, HsLds *lds, int w, int pass, uint32_t s, uint32_t lo, uint32_t end,
+                          uint32_t slice)
 {
-    const uint32_t slice = hs_slice(t.m);
-    const uint32_t lo = (uint32_t)w * slice;
     const int nbits = pass == 0 ? 8 : 7;
     uint32_t *off = pass == 0 ? lds->cnt0 : lds->cnt1;
-
-    for (uint32_t s = lo; s < lo + slice && s < t.m; s += WAVE) {
-        LANEVAR(uint32_t, ent);
-        LANEVAR(uint32_t, dig);
-        LANEVAR(int, ok);
+    LANEARR(uint32_t, ent, HS_SCATTER_BATCH);
+    LANEARR(uint32_t, dst, HS_SCATTER_BATCH);
+    /* 1. the loads of every step: pass 0 the input word of every position, pass 1 its entry in tmp
+     * (a lane without a position loads the wave's first one over again and drops it) */
+    UNROLL_FULL
+    for (uint32_t k = 0; k < HS_SCATTER_BATCH; k++) {
         FOR_LANES
         {
-            uint32_t i = s + (uint32_t)LANE;
-            LV(ok) = i < t.m;
-            uint32_t e = 0;
-            if (LV(ok)) {
-                if (pass == 0) {
-                    uint32_t h = hs_hash3(t.in, t.start + i, t.n);
-                    e = i | (h << 16);
-                } else {
-                    e = t.tmp[i];
+            const uint32_t i = s + k * WAVE + (uint32_t)LANE;
+            const uint32_t ii = FULL || i < end ? i : lo;
+            LVA(ent, k) = pass == 0 ? hs_word3(t.in, t.start + ii, t.n) : t.tmp[ii];
+            LVA(dst, k) = 0;
+        }
+    }
+    /* 2. where every entry goes, step by step in ascending order: a step reads the offsets of its
+     * digits and moves them past its own entries before the next step reads them (stability) */
+    UNROLL_FULL
+    for (uint32_t k = 0; k < HS_SCATTER_BATCH; k++) {
+        if (FULL || s + k * WAVE < end) {
+            LANEVAR(uint32_t, dig);
+            LANEVAR(int, ok);
+            FOR_LANES
+            {
+                const uint32_t i = s + k * WAVE + (uint32_t)LANE;
+                LV(ok) = FULL || i < end;
+                if (pass == 0) /* the entry of the position from its input word */
+                    LVA(ent, k) = i | (hs_hash_word(LVA(ent, k)) << 16);
+                LV(dig) = pass == 0 ? ((LVA(ent, k) >> 16) & 0xff) : (LVA(ent, k) >> 24);
+            }
+            /* ballot multi-split: lanes with the same digit find each other */
+            LANEVAR(uint64_t, peers);
+            uint64_t live = BALLOT(ok);
+            FOR_LANES { LV(peers) = live; }
+            for (int b = 0; b < nbits; b++) {
+                LANEVAR(int, bit);
+                FOR_LANES { LV(bit) = (int)((LV(dig) >> b) & 1u); }
+                uint64_t ones = BALLOT(bit);
+                FOR_LANES { LV(peers) &= LV(bit) ? ones : ~ones; }
+            }
+            FOR_LANES
+            {
+                if (LV(ok)) {
+                    uint32_t before = (uint32_t)POPC64(LV(peers) & ((1ull << LANE) - 1ull));
+                    LVA(dst, k) = off[LV(dig) * HS_WAVES + (uint32_t)w] + before;
                 }
             }
-            LV(ent) = e;
-            LV(dig) = pass == 0 ? ((e >> 16) & 0xff) : (e >> 24);
-        }
-        /* ballot multi-split: lanes with the same digit find each other */
-        LANEVAR(uint64_t, peers);
-        uint64_t live = BALLOT(ok);
-        FOR_LANES { LV(peers) = live; }
-        for (int b = 0; b < nbits; b++) {
-            LANEVAR(int, bit);
-            FOR_LANES { LV(bit) = (int)((LV(dig) >> b) & 1u); }
-            uint64_t ones = BALLOT(bit);
-            FOR_LANES { LV(peers) &= LV(bit) ? ones : ~ones; }
-        }
-        LANEVAR(uint32_t, dst);
-        FOR_LANES
-        {
-            if (LV(ok)) {
-                uint32_t before = (uint32_t)POPC64(LV(peers) & ((1ull << LANE) - 1ull));
-                LV(dst) = off[LV(dig) * HS_WAVES + (uint32_t)w] + before;
-            }
-        }
-        FOR_LANES
-        {
-            if (LV(ok)) {
-                uint64_t mine = LV(peers);
-                if ((mine & ((1ull << LANE) - 1ull)) == 0) /* first lane of its digit group */
-                    off[LV(dig) * HS_WAVES + (uint32_t)w] += (uint32_t)POPC64(mine);
-            }
-        }
-        FOR_LANES
-        {
-            if (LV(ok)) {
-                if (pass == 0) {
-                    t.tmp[LV(dst)] = LV(ent);
-                    /* the second pass counts its digits per wave slice of tmp: where this entry
-                     * lands decides the slice, so that count is taken here and the counting
-                     * pass over tmp is saved */
-                    LDS_ADD_U32(&lds->cnt1[(LV(ent) >> 24) * HS_WAVES + LV(dst) / slice], 1u);
-                } else {
-                    t.sorted[LV(dst)] = LV(ent);
-                    t.rank[t.start + (LV(ent) & ZD_TILE_MASK)] = (uint16_t)LV(dst);
+            FOR_LANES
+            {
+                if (LV(ok)) {
+                    uint64_t mine = LV(peers);
+                    if ((mine & ((1ull << LANE) - 1ull)) == 0) /* first lane of its digit group */
+                        off[LV(dig) * HS_WAVES + (uint32_t)w] += (uint32_t)POPC64(mine);
                 }
             }
         }
     }
+    /* 3. the stores of every step */
+    UNROLL_FULL
+    for (uint32_t k = 0; k < HS_SCATTER_BATCH; k++) {
+        FOR_LANES
+        {
+            if (FULL || s + k * WAVE + (uint32_t)LANE < end) {
+                if (pass == 0) {
+                    t.tmp[LVA(dst, k)] = LVA(ent, k);
+                    /* the second pass counts its digits per wave slice of tmp: where this entry
+                     * lands decides the slice, so that count is taken here and the counting
+                     * pass over tmp is saved */
+                    LDS_ADD_U32(&lds->cnt1[(LVA(ent, k) >> 24) * HS_WAVES + LVA(dst, k) / slice], 1u);
+                } else {
+                    t.sorted[LVA(dst, k)] = LVA(ent, k);
+                    t.rank[t.start + (LVA(ent, k) & ZD_TILE_MASK)] = (uint16_t)LVA(dst, k);
+                }
+            }
+        }
+    }
+}
+
+/* stable scatter of one pass; pass 1 reads its entries from tmp */
+DEV void hs_scatter(const HsTile &t, HsLds *lds, int w, int pass)
+{
+    const uint32_t slice = hs_slice(t.m);
+    const uint32_t lo = (uint32_t)w * slice;
+    const uint32_t end = lo + slice < t.m ? lo + slice : t.m; /* the wave's positions are [lo, end) */
+    uint32_t s = lo;
+    for (; s + HS_SCATTER_BATCH * WAVE <= end; s += HS_SCATTER_BATCH * WAVE)
+        hs_scatter_batch<true>(t, lds, w, pass, s, lo, end, slice);
+    if (s < end) /* fewer steps than a batch, or a last step that is not full */
+        hs_scatter_batch<false>(t, lds, w, pass, s, lo, end, slice);
 }
 
 DEV void hs_count(const HsTile &t, HsLds *lds, int w, int pass)
@@ -197,15 +239,31 @@ DEV void hs_scan(uint32_t *cnt, int ndig)
 DEV void hs_directory(const HsTile &t, int w)
 {
     /* bucket starts: sorted index i opens every bucket in (h[i-1], h[i]] */
-    for (uint32_t s = (uint32_t)w * WAVE; s < t.m; s += HS_WAVES * WAVE) {
-        FOR_LANES
-        {
-            uint32_t i = s + (uint32_t)LANE;
-            if (i < t.m) {
-                uint32_t h = t.sorted[i] >> 16;
-                int32_t hp = i == 0 ? -1 : (int32_t)(t.sorted[i - 1] >> 16);
-                for (int32_t hh = hp + 1; hh <= (int32_t)h; hh++)
-                    t.dir[hh] = (uint16_t)i;
+    /* (the loads of HS_SCATTER_BATCH steps before the first store, as in hs_scatter) */
+    for (uint32_t s = (uint32_t)w * WAVE; s < t.m; s += HS_SCATTER_BATCH * HS_WAVES * WAVE) {
+        LANEARR(uint32_t, cur, HS_SCATTER_BATCH);
+        LANEARR(uint32_t, prv, HS_SCATTER_BATCH);
+        UNROLL_FULL
+        for (uint32_t k = 0; k < HS_SCATTER_BATCH; k++) {
+            FOR_LANES
+            {
+                const uint32_t i = s + k * HS_WAVES * WAVE + (uint32_t)LANE;
+                const uint32_t ii = i < t.m ? i : 0; /* (a lane past m loads entry 0 and drops it) */
+                LVA(cur, k) = t.sorted[ii];
+                LVA(prv, k) = t.sorted[ii ? ii - 1 : 0]; /* (not used where i is 0) */
+            }
+        }
+        UNROLL_FULL
+        for (uint32_t k = 0; k < HS_SCATTER_BATCH; k++) {
+            FOR_LANES
+            {
+                const uint32_t i = s + k * HS_WAVES * WAVE + (uint32_t)LANE;
+                if (i < t.m) {
+                    const int32_t h = (int32_t)(LVA(cur, k) >> 16);
+                    const int32_t hp = i == 0 ? -1 : (int32_t)(LVA(prv, k) >> 16);
+                    for (int32_t hh = hp + 1; hh <= h; hh++)
+                        t.dir[hh] = (uint16_t)i;
+                }
             }
         }
     }
