@@ -491,6 +491,86 @@ ZlibReturn zsc_hip_uncompress_indexed_batch(U32 count, const U8 *const *sources,
                                             I32 window_bits, const U8 *const *indexes,
                                             const uint64_t *index_lens);
 
+/* packed images ---------------------------------------------------------------- */
+
+/* A plan leaves item i where its layout put it: at out_offsets[i] (deflate) or dst_offsets[i] (inflate), in a
+ * slot sized for the worst case, and how long each item is, is known on the device only.  Packing moves the
+ * items of the last run into ONE dense image, item after item, with a table of offsets, without a trip to the
+ * host in between (zsc_amd/csrc/pack.h): an exclusive prefix sum of the lengths on the
+ * device -- reduce, scan of the sums and apply as launches of their own, one to seven of them by count -- and
+ * one launch that moves the bytes, a wavefront per ZSC_HIP_PACK_TILE bytes of the image.
+ *
+ * The length of an item is read from the plan's result records on the device: of a deflate plan out_len where
+ * the status is Z_OK and 0 otherwise; of an inflate plan the dest_len that _results reports, whatever the
+ * status, so that the salvaged output of a damaged stream is kept.
+ *
+ * align: a power of two from 1 to 4096 (anything else: Z_STREAM_ERROR); every item starts at a multiple of it
+ *   and the bytes between an item's end and the next start are written as zeros, so the image is a function
+ *   of the items alone.  16 or more gives offsets an inflate plan takes as its src_offsets (the image then
+ *   needs 64 readable bytes behind it, as every inflate input does); 1 gives an archive -- gzip streams packed
+ *   with align 1 are a valid multi-member gzip file.
+ *
+ * _pack_enable: before _run, for plans of every kind (deflate: Z_STREAM_ERROR for a plan of sections).
+ *   Allocates 16 bytes per item (the dense offsets and the slots' offsets), 8 more for the total and 8 per
+ *   1 024 items for the scan's partial sums, counted in _scratch_bytes.  Calling it again with another align
+ *   only changes the align.  A plan that never enables packing allocates, launches and returns exactly what
+ *   it did without these functions.  The index and verification of a deflate plan may be enabled too; they
+ *   keep referring to the plan's own out_offsets, that is to the stream where the run wrote it, not to the
+ *   packed image.
+ * _pack: asynchronous on hip_stream; enqueues kernels only -- no allocation, no synchronisation, no copy from
+ *   or to the host.  Valid after a _run on the same stream or after _results, any number of times (an inflate
+ *   plan that resynchronises damaged streams finishes them in _results: pack such a plan after _results).
+ *   d_output is the run's output or a copy of it at the plan's offsets, as with _verify; of each item the
+ *   pack reads the whole 16-byte granules that hold one of its bytes, so never before its slot and at most 15
+ *   bytes behind its end.  d_packed is 16-byte aligned and packed_cap bytes long: bytes [0, total) are each
+ *   written exactly once and nothing at or behind total; with total > packed_cap nothing is written at all.
+ * _pack_results: waits for the last _pack.  offsets[i] (may be NULL): where item i starts, offsets[count] ==
+ *   *total; ms (may be NULL): the device time of that pack's launches, from HIP events on its stream.
+ *   Z_BUF_ERROR where total > packed_cap -- offsets and total are filled all the same, so that the caller can
+ *   size another _pack --; Z_STREAM_ERROR on a plan that never enabled packing or never packed. */
+#define ZSC_HIP_PACK_TILE 16384 /* bytes of the image one wavefront moves */
+
+ZlibReturn zsc_hip_deflate_plan_pack_enable(zsc_hip_deflate_plan *plan, U32 align);
+ZlibReturn zsc_hip_deflate_plan_pack(zsc_hip_deflate_plan *plan, const void *d_output, void *d_packed,
+                                     uint64_t packed_cap, void *hip_stream);
+ZlibReturn zsc_hip_deflate_plan_pack_results(zsc_hip_deflate_plan *plan, uint64_t *offsets, uint64_t *total,
+                                             float *ms);
+ZlibReturn zsc_hip_inflate_plan_pack_enable(zsc_hip_inflate_plan *plan, U32 align);
+ZlibReturn zsc_hip_inflate_plan_pack(zsc_hip_inflate_plan *plan, const void *d_output, void *d_packed,
+                                     uint64_t packed_cap, void *hip_stream);
+ZlibReturn zsc_hip_inflate_plan_pack_results(zsc_hip_inflate_plan *plan, uint64_t *offsets, uint64_t *total,
+                                             float *ms);
+
+/* The other way, without a plan: item i, lens[i] bytes at packed_offsets[i] of the image d_packed (16-byte
+ * aligned base, offsets of any alignment), goes to [dst_offsets[i], + lens[i]) of d_dst, and no other byte of
+ * d_dst is written.  The items lie in the image in ascending order without overlap (packed_offsets[i] +
+ * lens[i] <= packed_offsets[i + 1]; what lies between them is skipped) and dst_offsets are multiples of 16:
+ * Z_STREAM_ERROR otherwise.  Nothing of the image is read at or behind the last item's end.  The three host
+ * arrays are uploaded before the call returns; the launch is asynchronous on hip_stream. */
+ZlibReturn zsc_hip_unpack(U32 count, const void *d_packed, const uint64_t *packed_offsets, const U32 *lens,
+                          void *d_dst, const uint64_t *dst_offsets, void *hip_stream);
+
+/* Host images: zsc_hip_compress_batch / zsc_hip_uncompress_batch for a caller whose items lie in one host
+ * buffer -- one copy to the device and one back, whatever count is, where the pointer batches do one per item
+ * each way.  The image is uploaded with one hipMemcpy, unpacked into a plan's layout, the same plan as the
+ * pointer batch's runs, its results are packed and bytes [0, total) come back with one hipMemcpy.  Statuses
+ * (and consumed) are those of the pointer batches given enough room.
+ *
+ * zsc_hip_compress_batch_packed: buffer i is sources[source_offsets[i] .. source_offsets[i + 1]); stream i is
+ *   dest[dest_offsets[i] ...], dest_offsets[count] the image's length.  There is no capacity per item: the call
+ *   returns Z_BUF_ERROR where dest_cap is less than the image's length, with dest_offsets filled and dest
+ *   untouched.  Level 0 is Z_STREAM_ERROR (the store path hands out no plan).
+ * zsc_hip_uncompress_batch_packed: stream i is source_lens[i] bytes at sources[source_offsets[i]] (ascending,
+ *   no overlap); dest_caps[i] is the most it may decode to, as dest_lens[i] on entry of
+ *   zsc_hip_uncompress_batch; output i is dest_lens[i] bytes at dest[dest_offsets[i]]. */
+ZlibReturn zsc_hip_compress_batch_packed(U32 count, const U8 *sources, const uint64_t *source_offsets, U8 *dest,
+                                         uint64_t dest_cap, uint64_t *dest_offsets, I32 *statuses, I32 level,
+                                         I32 window_bits, I32 mem_level, ZlibStrategy strategy, U32 align);
+ZlibReturn zsc_hip_uncompress_batch_packed(U32 count, const U8 *sources, const uint64_t *source_offsets,
+                                           const U32 *source_lens, const U32 *dest_caps, U8 *dest,
+                                           uint64_t dest_cap, uint64_t *dest_offsets, U32 *dest_lens,
+                                           U32 *consumed, I32 *statuses, I32 window_bits, U32 align);
+
 #ifdef __cplusplus
 }
 #endif

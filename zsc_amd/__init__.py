@@ -18,6 +18,9 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
   (``DeflatePlan.index_enable`` / ``export_indexes``): no chunks plan is ever needed for them;
 * :func:`compress_batch_verified` -- streams checked against their input on the device, block by block,
   before they leave it (``DeflatePlan.verify_enable`` / ``verify`` / ``verify_results``);
+* :func:`compress_batch_packed`, :func:`uncompress_batch_packed`, :func:`unpack` -- batches as ONE image with a
+  table of offsets: one copy to the device and one back whatever the count (``DeflatePlan.pack_enable`` /
+  ``pack`` / ``pack_results``, the same on :class:`InflatePlan`);
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -34,5 +37,6 @@ from .api import (  # noqa: F401
     uncompress_indexed_batch, build_indexes, index_info, index_range, compress_batch_indexed,
     compress_batch_verified, VERIFY_OK, VERIFY_SKIPPED, VERIFY_HEADER, VERIFY_BLOCK_HDR, VERIFY_CODES, VERIFY_LITERAL,
     VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH, VERIFY_BIT_END, VERIFY_TRAILER,
+    PACK_TILE, unpack, compress_batch_packed, uncompress_batch_packed, PackedCallError,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

@@ -20,6 +20,7 @@ Z_ERRNO, Z_STREAM_ERROR, Z_DATA_ERROR, Z_MEM_ERROR, Z_BUF_ERROR, Z_VERSION_ERROR
 Z_DEFAULT_STRATEGY, Z_FILTERED, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED = 0, 1, 2, 3, 4
 GZIP_CODE, DEF_WBITS, DEF_MEM_LEVEL = 16, 15, 8
 NKERNELS = 9
+PACK_TILE = 16384  # ZSC_HIP_PACK_TILE: bytes of a packed image one wavefront moves
 KERNEL_NAMES = ("checksum", "hash_sort", "match_table", "parse", "parse_short", "huff_plan", "layout", "emit", "total")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -148,6 +149,15 @@ def _load() -> C.CDLL:
     L.zsc_hip_deflate_plan_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.zsc_hip_deflate_plan_verify_results.argtypes = [C.c_void_p, C.POINTER(VerifyResult), C.POINTER(C.c_float)]
     L.zsc_hip_deflate_plan_verify_blocks.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(VerifyBlock), C.c_uint32, u32p]
+    for kind in ("deflate", "inflate"):
+        getattr(L, f"zsc_hip_{kind}_plan_pack_enable").argtypes = [C.c_void_p, C.c_uint32]
+        getattr(L, f"zsc_hip_{kind}_plan_pack").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        getattr(L, f"zsc_hip_{kind}_plan_pack_results").argtypes = [C.c_void_p, u64p, u64p, C.POINTER(C.c_float)]
+    L.zsc_hip_unpack.argtypes = [C.c_uint32, C.c_void_p, u64p, u32p, C.c_void_p, u64p, C.c_void_p]
+    L.zsc_hip_compress_batch_packed.argtypes = [C.c_uint32, C.c_char_p, u64p, C.c_void_p, C.c_uint64, u64p, i32p,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
+    L.zsc_hip_uncompress_batch_packed.argtypes = [C.c_uint32, C.c_char_p, u64p, u32p, u32p, C.c_void_p, C.c_uint64,
+                                                  u64p, u32p, u32p, i32p, C.c_int32, C.c_uint32]
     return L
 
 
@@ -502,6 +512,118 @@ def compress_batch_verified(sources: Sequence[bytes], level: int = 6, window_bit
         plan.close()
 
 
+def _round_up(n: int, align: int) -> int:
+    return (n + align - 1) // align * align if align > 1 else n  # (an align the library refuses: no matter)
+
+
+class PackedCallError(RuntimeError):
+    """A *_batch_packed call that did not run: .rc is the ZlibReturn (Z_STREAM_ERROR: level 0, an align that is
+    no power of two from 1 to 4096, offsets out of order; Z_BUF_ERROR: dest_cap is too small, and .offsets[-1]
+    says what the image takes)."""
+
+    def __init__(self, what: str, rc: int, offsets: List[int]):
+        super().__init__(f"{what} failed: {rc}")
+        self.rc, self.offsets = rc, offsets
+
+
+class _Packing:
+    """pack_enable / pack / pack_results / pack_ms of both plan classes (zsc_hip_*_plan_pack*)."""
+    _pack_kind = ""
+
+    def pack_enable(self, align: int = 16) -> None:
+        """Before run(): the plan can pack the items of a run into one image, item i at a multiple of align (a
+        power of two from 1 to 4096; 16 or more feeds InflatePlan(src_offsets=...), 1 gives an archive)."""
+        rc = getattr(lib, f"zsc_hip_{self._pack_kind}_plan_pack_enable")(self._h, align)
+        if rc != Z_OK:
+            raise ValueError(f"zsc_hip_{self._pack_kind}_plan_pack_enable failed: {rc}")
+
+    def pack(self, d_output: int, d_packed: int, cap: int, stream: int = 0) -> int:
+        """After run() on the same stream, or after results(), any number of times: enqueue the pack of the
+        items at d_output (the run's output or a copy of it at the plan's offsets) into the cap bytes at
+        d_packed (16-byte aligned).  Returns the ZlibReturn: Z_STREAM_ERROR on a plan without pack_enable()."""
+        return getattr(lib, f"zsc_hip_{self._pack_kind}_plan_pack")(self._h, C.c_void_p(d_output), C.c_void_p(d_packed),
+                                                                     cap, C.c_void_p(stream))
+
+    def pack_results(self) -> Tuple[List[int], int]:
+        """Waits for the last pack(): (offsets, total) -- count + 1 offsets, the last one the total.  BufferError,
+        with .offsets and .total to size another pack() by, where the image was longer than cap (nothing was
+        written then)."""
+        off = (C.c_uint64 * (self.count + 1))()
+        total, ms = C.c_uint64(), C.c_float()
+        rc = getattr(lib, f"zsc_hip_{self._pack_kind}_plan_pack_results")(self._h, off, C.byref(total), C.byref(ms))
+        self._pack_ms = ms.value
+        if rc == Z_BUF_ERROR:
+            err = BufferError(f"the packed image takes {total.value} bytes")
+            err.offsets, err.total = list(off), total.value
+            raise err
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_{self._pack_kind}_plan_pack_results failed: {rc}")
+        return list(off), total.value
+
+    def pack_ms(self) -> float:
+        """After pack_results(): device time of that pack's launches, in milliseconds."""
+        if getattr(self, "_pack_ms", None) is None:
+            raise RuntimeError("no pack_results() yet")
+        return self._pack_ms
+
+
+def unpack(d_packed: int, packed_offsets: Sequence[int], lens: Sequence[int], d_dst: int,
+           dst_offsets: Sequence[int], stream: int = 0) -> int:
+    """zsc_hip_unpack: item i, lens[i] bytes at packed_offsets[i] of the device image d_packed (ascending, any
+    alignment; a count + 1 table as pack_results() returns it will do), to dst_offsets[i] (multiples of 16) of
+    d_dst; no other byte of d_dst is written.  Asynchronous on stream.  Returns the ZlibReturn."""
+    n = len(lens)
+    return lib.zsc_hip_unpack(n, C.c_void_p(d_packed), (C.c_uint64 * n)(*packed_offsets[:n]), (C.c_uint32 * n)(*lens),
+                              C.c_void_p(d_dst), (C.c_uint64 * n)(*dst_offsets), C.c_void_p(stream))
+
+
+def compress_batch_packed(sources, level: int = 6, window_bits: int = DEF_WBITS, mem_level: int = DEF_MEM_LEVEL,
+                          strategy: int = Z_DEFAULT_STRATEGY, align: int = 1, source_offsets: Sequence[int] | None = None,
+                          dest_cap: Optional[int] = None) -> Tuple[bytes, List[int], List[int]]:
+    """zsc_hip_compress_batch_packed: compress_batch with one copy to the device and one back.  sources: a
+    sequence of buffers, or one bytes object with source_offsets (count + 1).  Returns (image, offsets,
+    statuses): stream i is image[offsets[i]:offsets[i + 1]] less its padding up to align; with align 1 the
+    image is the streams one after the other.  PackedCallError where the call as a whole fails."""
+    if source_offsets is None:
+        source_offsets = [0]
+        for s_ in sources:
+            source_offsets.append(source_offsets[-1] + len(s_))
+        sources = b"".join(sources)
+    n = len(source_offsets) - 1
+    if dest_cap is None:
+        dest_cap = sum(_round_up(compress_get_max_output_size2(source_offsets[i + 1] - source_offsets[i],
+                                                               max(source_offsets[i + 1] - source_offsets[i], 1), level,
+                                                               window_bits, mem_level)[1], align) for i in range(n))
+    dst = C.create_string_buffer(max(dest_cap, 1))
+    off = (C.c_uint64 * (n + 1))()
+    stat = (C.c_int32 * max(n, 1))()
+    rc = lib.zsc_hip_compress_batch_packed(n, sources, (C.c_uint64 * (n + 1))(*source_offsets), dst, dest_cap, off,
+                                           stat, level, window_bits, mem_level, strategy, align)
+    if rc != Z_OK:
+        raise PackedCallError("zsc_hip_compress_batch_packed", rc, list(off))
+    return dst.raw[:off[n]], list(off), list(stat)[:n]
+
+
+def uncompress_batch_packed(image: bytes, offsets: Sequence[int], lens: Sequence[int], dest_caps: Sequence[int],
+                            window_bits: int = DEF_WBITS, align: int = 1, dest_cap: Optional[int] = None):
+    """zsc_hip_uncompress_batch_packed: uncompress_batch with one copy to the device and one back.  Stream i is
+    lens[i] bytes at image[offsets[i]] (ascending; a count + 1 table will do) and may decode to dest_caps[i]
+    bytes.  Returns (image, offsets, dest_lens, consumed, statuses): output i is dest_lens[i] bytes at
+    offsets[i] of the returned image.  PackedCallError where the call as a whole fails."""
+    n = len(lens)
+    if dest_cap is None:
+        dest_cap = sum(_round_up(c, align) for c in dest_caps)
+    dst = C.create_string_buffer(max(dest_cap, 1))
+    off = (C.c_uint64 * (n + 1))()
+    dlen, used, stat = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    rc = lib.zsc_hip_uncompress_batch_packed(n, image, (C.c_uint64 * max(n, 1))(*offsets[:n]), (C.c_uint32 * max(n, 1))(*lens),
+                                             (C.c_uint32 * max(n, 1))(*dest_caps), dst, dest_cap, off, dlen, used, stat,
+                                             window_bits, align)
+    if rc != Z_OK:
+        raise PackedCallError("zsc_hip_uncompress_batch_packed", rc, list(off))
+    return dst.raw[:off[n]], list(off), list(dlen)[:n], list(used)[:n], list(stat)[:n]
+
+
 def _uncompress_batch(fn, sources, dest_caps, window_bits):
     count = len(sources)
     srcs = (C.c_char_p * count)(*sources)
@@ -515,7 +637,7 @@ def _uncompress_batch(fn, sources, dest_caps, window_bits):
     return rc, outs, list(slen), list(stat)
 
 
-class InflatePlan:
+class InflatePlan(_Packing):
     """Device-resident inflate batch (see include/zsc_hip.h).  sections=True makes a sections plan
     (zsc_hip_inflate_plan_create_sections: full-flush sections decoded in parallel; it takes no
     decode_order).  chunks=True makes a chunks plan (zsc_hip_inflate_plan_create_chunks: any stream longer
@@ -526,13 +648,17 @@ class InflatePlan:
     export_index().  indexes=[blob or None, ...] makes an indexed plan (zsc_hip_inflate_plan_create_indexed:
     every stream with a valid index decoded in parallel from its seek points); with it, ranges=[(begin,
     length) or None, ...] decodes only the whole pieces that cover that range of the stream's output
-    (index_range), to the start of the stream's destination."""
+    (index_range), to the start of the stream's destination.  src_offsets=[...] (multiples of 16) puts the
+    streams where the caller has them instead of one behind the other -- the offsets of an image packed with
+    align 16 or more, say, which then is the plan's input as it lies; src_bytes is not meaningful then."""
+    _pack_kind = "inflate"
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int],
                  window_bits: int = DEF_WBITS, decode_order: Sequence[int] | None = None,
                  sections: bool = False, chunks: bool = False, chunk_bytes: int = 0, resync: bool = False,
                  keep_index: bool = False, indexes: Sequence[Optional[bytes]] | None = None,
-                 ranges: Sequence[Optional[Tuple[int, int]]] | None = None):
+                 ranges: Sequence[Optional[Tuple[int, int]]] | None = None,
+                 src_offsets: Sequence[int] | None = None):
         self.count = n = len(source_lens)
         if keep_index and not chunks:
             raise ValueError("keep_index needs a chunks plan")
@@ -546,6 +672,11 @@ class InflatePlan:
             do.append(db)
             sb += (sl + 64 + 15) & ~15
             db += (dc + 64 + 15) & ~15
+        if src_offsets is not None:
+            if len(src_offsets) != n:
+                raise ValueError("one source offset per stream")
+            so = list(src_offsets)
+            sb = max([o + l for o, l in zip(so, source_lens)], default=0)
         self.src_offsets, self.dst_offsets = so, do
         self.src_bytes, self.dst_bytes = sb + 64, db + 64
         self._h = C.c_void_p()
@@ -654,16 +785,19 @@ class InflatePlan:
             pass
 
 
-class DeflatePlan:
+class DeflatePlan(_Packing):
     """A device-resident batch: fixed buffer lengths, inputs/outputs stay in HBM.
 
     ``layout`` gives the byte offsets of every buffer inside one input and one output
     allocation; ``run`` takes raw device pointers (e.g. ``tensor.data_ptr()``), so the
-    binding itself needs neither torch nor numpy.
+    binding itself needs neither torch nor numpy.  ``out_caps`` (default: the layout's own, the worst case)
+    gives stream i less room than that: a stream that does not fit ends in Z_BUF_ERROR.
     """
+    _pack_kind = "deflate"
 
     def __init__(self, source_lens: Sequence[int], level: int = 6, window_bits: int = DEF_WBITS,
-                 mem_level: int = DEF_MEM_LEVEL, strategy: int = Z_DEFAULT_STRATEGY):
+                 mem_level: int = DEF_MEM_LEVEL, strategy: int = Z_DEFAULT_STRATEGY,
+                 out_caps: Sequence[int] | None = None):
         self.count = n = len(source_lens)
         self.source_lens = list(source_lens)
         lens = (C.c_uint32 * n)(*source_lens)
@@ -676,6 +810,10 @@ class DeflatePlan:
         if rc != Z_OK:
             raise ValueError(f"zsc_hip_deflate_plan_layout failed: {rc}")
         self.in_bytes, self.out_bytes = ib.value, ob.value
+        if out_caps is not None:
+            if len(out_caps) != n or any(c > full for c, full in zip(out_caps, self._caps)):
+                raise ValueError("one capacity per buffer, none above the layout's")
+            self._caps = (C.c_uint32 * n)(*out_caps)
         self.in_offsets = list(self._in_off)
         self.out_offsets = list(self._out_off)
         self.out_caps = list(self._caps)

@@ -32,6 +32,7 @@
 #include "inflate_index.h"
 #include "deflate_index.h"
 #include "deflate_verify.h"
+#include "pack.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "lz_parse_pipe.h"
@@ -724,6 +725,35 @@ __global__ __launch_bounds__(64) void k_verify_finish(const uint8_t *__restrict_
                wbits, level, strategy, &results[b]);
 }
 
+/* kernels 4i-4l (pack.h): a plan's results packed into one image, only for a plan with packing enabled, and
+ * zsc_hip_unpack.  The offsets: one wavefront per PK_SCAN_B values of a level of the scan -- 4i the sums of a
+ * level that one wavefront cannot take alone, 4j the scan of the top level by one wavefront, 4k the levels
+ * below it with the bases from the level above.  vals == null: the values are the item lengths rounded up to
+ * align; out may be vals */
+__global__ __launch_bounds__(64) void k_pack_reduce(PkLens lens, uint32_t align, const uint64_t *vals, uint64_t n,
+                                                    uint64_t *sums)
+{
+    pk_scan_block(lens, align, vals, n, blockIdx.x, nullptr, nullptr, sums);
+}
+
+__global__ __launch_bounds__(64) void k_pack_scan_sums(PkLens lens, uint32_t align, const uint64_t *vals, uint64_t n,
+                                                       uint64_t *out)
+{
+    pk_scan_block(lens, align, vals, n, 0, nullptr, out, nullptr);
+}
+
+__global__ __launch_bounds__(64) void k_pack_apply(PkLens lens, uint32_t align, const uint64_t *vals, uint64_t n,
+                                                   const uint64_t *base, uint64_t *out)
+{
+    pk_scan_block(lens, align, vals, n, blockIdx.x, base, out, nullptr);
+}
+
+/* 4l: one wavefront per tile of the dense image, in either direction */
+__global__ __launch_bounds__(64) void k_pack_move(PkMove M, uint8_t *dense, uint8_t *sparse)
+{
+    pk_move_tile(M, dense, sparse, blockIdx.x);
+}
+
 /* one stream of an inflate batch */
 typedef struct {
     uint64_t src_off, dst_off;
@@ -1214,6 +1244,192 @@ struct SubBatch {
     uint32_t cseg = 0;  /* [0,cseg) of the length-sorted order go to the segmented parser */
 };
 
+/* Packing (pack.h): what a plan of either kind holds for it, and the launches */
+struct PackState {
+    bool on = false, ran = false;
+    uint32_t count = 0, align = 0;
+    std::vector<uint32_t> caps; /* the most each item takes */
+    uint64_t max_total = 0;     /* ... and the image */
+    uint64_t cap = 0;           /* packed_cap of the last pack */
+    DevBuf d_off;               /* count + 1 dense offsets, written by every pack */
+    DevBuf d_sparse;            /* count slot offsets */
+    DevBuf d_sums;              /* the scan's levels above the items: n[k] + 1 values each */
+    uint32_t levels = 1;
+    uint64_t level_n[PK_MAX_LEVELS] = {0}, level_at[PK_MAX_LEVELS] = {0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    uint64_t scratch = 0;
+};
+
+bool pack_align_ok(U32 align)
+{
+    return align >= 1u && align <= 4096u && (align & (align - 1u)) == 0u;
+}
+
+void pack_set_align(PackState &ps, U32 align)
+{
+    ps.align = align;
+    ps.max_total = 0;
+    for (uint32_t c : ps.caps)
+        ps.max_total += ((uint64_t)c + (align - 1u)) & ~(uint64_t)(align - 1u);
+}
+
+void pack_release(PackState &ps, uint64_t *scratch_bytes)
+{
+    ps.d_off.release();
+    ps.d_sparse.release();
+    ps.d_sums.release();
+    for (hipEvent_t &e : ps.ev) {
+        if (e)
+            (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    if (scratch_bytes)
+        *scratch_bytes -= ps.scratch;
+    ps.scratch = 0;
+    ps.on = ps.ran = false;
+}
+
+ZlibReturn pack_setup(PackState &ps, uint32_t count, U32 align, const uint64_t *sparse_off, const U32 *caps,
+                      uint64_t *scratch_bytes)
+{
+    ps.count = count;
+    ps.caps.assign(caps, caps + count);
+    pack_set_align(ps, align);
+    ps.levels = pk_scan_levels(count, ps.level_n);
+    uint64_t nsums = 0;
+    for (uint32_t k = 1; k < ps.levels; k++) {
+        ps.level_at[k] = nsums;
+        nsums += ps.level_n[k] + 1u;
+    }
+    bool ok = ps.d_off.ensure(((uint64_t)count + 1u) * 8u) && ps.d_sparse.ensure(std::max<uint64_t>(count, 1) * 8u) &&
+              ps.d_sums.ensure(std::max<uint64_t>(nsums, 1) * 8u);
+    ok = ok && (count == 0 || hipMemcpy(ps.d_sparse.p, sparse_off, 8ull * count, hipMemcpyHostToDevice) == hipSuccess) &&
+         hipEventCreate(&ps.ev[0]) == hipSuccess && hipEventCreate(&ps.ev[1]) == hipSuccess;
+    ps.scratch = ps.d_off.bytes + ps.d_sparse.bytes + ps.d_sums.bytes;
+    *scratch_bytes += ps.scratch;
+    if (!ok) {
+        (void)hipGetLastError();
+        pack_release(ps, scratch_bytes);
+        return Z_MEM_ERROR;
+    }
+    ps.on = true;
+    return Z_OK;
+}
+
+/* the dense offsets of the items whose lengths `lens` names: reduce up the levels, scan the top one, apply down */
+void pack_scan_enqueue(const PackState &ps, const PkLens &lens, hipStream_t st)
+{
+    uint64_t *const sums = (uint64_t *)ps.d_sums.p;
+    auto vals = [&](uint32_t k) { return k == 0 ? (uint64_t *)nullptr : sums + ps.level_at[k]; };
+    for (uint32_t k = 0; k + 1u < ps.levels; k++)
+        hipLaunchKernelGGL(k_pack_reduce, dim3((uint32_t)ps.level_n[k + 1u]), dim3(64), 0, st, lens, ps.align,
+                           (const uint64_t *)vals(k), ps.level_n[k], vals(k + 1u));
+    const uint32_t top = ps.levels - 1u;
+    hipLaunchKernelGGL(k_pack_scan_sums, dim3(1), dim3(64), 0, st, lens, ps.align, (const uint64_t *)vals(top),
+                       ps.level_n[top], top == 0 ? (uint64_t *)ps.d_off.p : vals(top));
+    for (uint32_t k = top; k-- > 0;)
+        hipLaunchKernelGGL(k_pack_apply, dim3((uint32_t)ps.level_n[k + 1u]), dim3(64), 0, st, lens, ps.align,
+                           (const uint64_t *)vals(k), ps.level_n[k], (const uint64_t *)vals(k + 1u),
+                           k == 0 ? (uint64_t *)ps.d_off.p : vals(k));
+}
+
+ZlibReturn pack_enqueue(PackState &ps, const PkLens &lens, const void *d_sparse_image, void *d_packed,
+                        uint64_t packed_cap, hipStream_t st)
+{
+    if (!ps.on || ((uintptr_t)d_packed & 15u) || ((uintptr_t)d_sparse_image & 15u))
+        return Z_STREAM_ERROR;
+    /* the grid comes from the capacity; what the image can be at the most bounds it */
+    const uint64_t tiles = (std::min(packed_cap, ps.max_total) + PK_TILE - 1u) / PK_TILE;
+    if (tiles > 0x7fffffffull)
+        return Z_MEM_ERROR;
+    if (tiles && (d_packed == Z_NULL || d_sparse_image == Z_NULL))
+        return Z_STREAM_ERROR;
+    (void)hipGetLastError();
+    if (ps.ran && ps.stream != st) /* the offsets of the one before may still be in use */
+        HIP_TRY(hipStreamSynchronize(ps.stream), return Z_STREAM_ERROR);
+    ps.stream = st;
+    ps.ran = true;
+    ps.cap = packed_cap;
+    (void)hipEventRecord(ps.ev[0], st);
+    pack_scan_enqueue(ps, lens, st);
+    if (tiles) {
+        PkMove M;
+        M.off = (const uint64_t *)ps.d_off.p;
+        M.sparse_off = (const uint64_t *)ps.d_sparse.p;
+        M.lens = lens;
+        M.count = ps.count;
+        M.unpack = 0;
+        M.cap = packed_cap;
+        hipLaunchKernelGGL(k_pack_move, dim3((uint32_t)tiles), dim3(64), 0, st, M, (uint8_t *)d_packed,
+                           (uint8_t *)const_cast<void *>(d_sparse_image));
+    }
+    (void)hipEventRecord(ps.ev[1], st);
+    HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
+    return Z_OK;
+}
+
+ZlibReturn pack_fetch(PackState &ps, uint64_t *offsets, uint64_t *total, float *ms)
+{
+    if (ms)
+        *ms = 0.f;
+    if (total)
+        *total = 0;
+    if (!ps.on || !ps.ran)
+        return Z_STREAM_ERROR;
+    HIP_TRY(hipStreamSynchronize(ps.stream), return Z_STREAM_ERROR);
+    uint64_t tot = 0;
+    if (offsets) {
+        HIP_TRY(hipMemcpy(offsets, ps.d_off.p, ((size_t)ps.count + 1u) * 8u, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+        tot = offsets[ps.count];
+    } else {
+        HIP_TRY(hipMemcpy(&tot, (const uint64_t *)ps.d_off.p + ps.count, 8, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    }
+    if (total)
+        *total = tot;
+    if (ms)
+        (void)hipEventElapsedTime(ms, ps.ev[0], ps.ev[1]);
+    return tot > ps.cap ? Z_BUF_ERROR : Z_OK;
+}
+
+/* dense image -> slots: the offsets are the caller's, so no scan; d_table: count + 1 dense offsets, d_lens: count
+ * lengths, d_slots: count slot offsets, all on the device already */
+void unpack_enqueue(uint32_t count, uint64_t total, const void *d_packed, const void *d_table, const void *d_lens,
+                    void *d_dst, const void *d_slots, hipStream_t st)
+{
+    const uint64_t tiles = (total + PK_TILE - 1u) / PK_TILE;
+    if (!tiles)
+        return;
+    PkMove M;
+    M.off = (const uint64_t *)d_table;
+    M.sparse_off = (const uint64_t *)d_slots;
+    M.lens.rec = (const uint32_t *)d_lens;
+    M.lens.stride_w = 1;
+    M.lens.len_w = 0;
+    M.lens.st_w = PK_NO_STATUS;
+    M.count = count;
+    M.unpack = 1;
+    M.cap = ~0ull;
+    hipLaunchKernelGGL(k_pack_move, dim3((uint32_t)tiles), dim3(64), 0, st, M,
+                       (uint8_t *)const_cast<void *>(d_packed), (uint8_t *)d_dst);
+}
+
+/* the host side of an unpack: the table of count + 1 offsets from the caller's; false where the items do not
+ * lie in ascending order without overlap, or a slot is not 16-byte aligned */
+bool unpack_table(uint32_t count, const uint64_t *packed_offsets, const U32 *lens, const uint64_t *dst_offsets,
+                  std::vector<uint64_t> &table)
+{
+    table.assign((size_t)count + 1u, 0);
+    for (uint32_t i = 0; i < count; i++) {
+        table[i] = packed_offsets[i];
+        const uint64_t end = packed_offsets[i] + lens[i];
+        if ((dst_offsets[i] & 15u) || end < packed_offsets[i] || (i + 1u < count && end > packed_offsets[i + 1u]))
+            return false;
+        table[i + 1u] = end;
+    }
+    return true;
+}
+
 } // namespace
 
 struct zsc_hip_deflate_plan {
@@ -1278,6 +1494,8 @@ struct zsc_hip_deflate_plan {
     uint64_t vf_scratch = 0;      /* what of scratch_bytes verification holds */
     hipEvent_t vf_ev[2] = {nullptr, nullptr};
     hipStream_t vf_stream = nullptr;
+    /* packing (pack.h), off unless zsc_hip_deflate_plan_pack_enable was called */
+    PackState pack;
 };
 
 namespace {
@@ -1961,6 +2179,8 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
     if (!pl)
         return;
     (void)hipStreamSynchronize(pl->last_stream); /* the blocks go back to the cache, not to hipFree */
+    if (pl->pack.ran)
+        (void)hipStreamSynchronize(pl->pack.stream);
     for (SubBatch &sb : pl->subs) {
         sb.d_bufs.release();
         sb.d_tile_owner.release();
@@ -1982,6 +2202,7 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
     pl->d_res.release();
     index_release(pl);
     verify_release(pl);
+    pack_release(pl->pack, &pl->scratch_bytes);
     for (hipEvent_t e : pl->events)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : pl->idx_events)
@@ -2268,6 +2489,50 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_verify_blocks(zsc_hip_deflate_plan *p
                           hipMemcpyDeviceToHost),
                 return Z_STREAM_ERROR);
     return Z_OK;
+}
+
+/* ---- packing a deflate plan's streams (pack.h) ------------------------------------------------ */
+
+static_assert(sizeof(ZdResult) == 16 && offsetof(ZdResult, out_len) == 0 && offsetof(ZdResult, status) == 4 &&
+                  sizeof(InfResult) == 16 && offsetof(InfResult, status) == 0 && offsetof(InfResult, out_len) == 4,
+              "the pack reads the lengths where the plans' results keep them");
+static_assert(PK_TILE % (16u * 64u) == 0, "a tile is whole steps of a wavefront");
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_pack_enable(zsc_hip_deflate_plan *pl, U32 align)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (pl->sectioned || !pack_align_ok(align))
+        return Z_STREAM_ERROR;
+    if (pl->pack.on) {
+        pack_set_align(pl->pack, align);
+        return Z_OK;
+    }
+    std::vector<uint64_t> slots(pl->count);
+    std::vector<U32> caps(pl->count);
+    for (uint32_t i = 0; i < pl->count; i++) {
+        slots[i] = pl->bufs[i].out_off;
+        caps[i] = pl->bufs[i].out_cap;
+    }
+    return pack_setup(pl->pack, pl->count, align, slots.data(), caps.data(), &pl->scratch_bytes);
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_pack(zsc_hip_deflate_plan *pl, const void *d_output, void *d_packed,
+                                                uint64_t packed_cap, void *hip_stream)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    /* a stream's length where its status is Z_OK, else 0 */
+    const PkLens lens = {(const uint32_t *)pl->d_res.p, 4u, 0u, 1u};
+    return pack_enqueue(pl->pack, lens, d_output, d_packed, packed_cap, (hipStream_t)hip_stream);
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_pack_results(zsc_hip_deflate_plan *pl, uint64_t *offsets, uint64_t *total,
+                                                        float *ms)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    return pack_fetch(pl->pack, offsets, total, ms);
 }
 
 /* ---- level 0 --------------------------------------------------------------------- */
@@ -3155,6 +3420,8 @@ struct zsc_hip_inflate_plan {
     hipStream_t last_stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
+    /* packing (pack.h), off unless zsc_hip_inflate_plan_pack_enable was called */
+    PackState pack;
 };
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_create_ordered(zsc_hip_inflate_plan **plan_out, U32 count,
@@ -3742,7 +4009,10 @@ extern "C" void zsc_hip_inflate_plan_destroy(zsc_hip_inflate_plan *pl)
     if (!pl)
         return;
     (void)hipStreamSynchronize(pl->last_stream);
+    if (pl->pack.ran)
+        (void)hipStreamSynchronize(pl->pack.stream);
     inflate_plan_release(pl);
+    pack_release(pl->pack, &pl->scratch_bytes);
     if (pl->ev0)
         (void)hipEventDestroy(pl->ev0);
     if (pl->ev1)
@@ -3982,6 +4252,274 @@ extern "C" ZlibReturn zsc_hip_uncompress_indexed_batch(U32 count, const U8 *cons
 {
     return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 4, indexes,
                                  index_lens);
+}
+
+/* ---- packing an inflate plan's outputs, unpacking, and the host images (pack.h) ----------------- */
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_pack_enable(zsc_hip_inflate_plan *pl, U32 align)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (!pack_align_ok(align))
+        return Z_STREAM_ERROR;
+    if (pl->pack.on) {
+        pack_set_align(pl->pack, align);
+        return Z_OK;
+    }
+    /* where the outputs go and how long they get at the most: the plan's own items */
+    std::vector<ZdInfItem> items(pl->count);
+    if (pl->count)
+        HIP_TRY(hipMemcpy(items.data(), pl->d_items.p, sizeof(ZdInfItem) * pl->count, hipMemcpyDeviceToHost),
+                return Z_STREAM_ERROR);
+    std::vector<uint64_t> slots(pl->count);
+    std::vector<U32> caps(pl->count);
+    for (uint32_t i = 0; i < pl->count; i++) {
+        slots[i] = items[i].dst_off;
+        caps[i] = items[i].dst_cap;
+    }
+    return pack_setup(pl->pack, pl->count, align, slots.data(), caps.data(), &pl->scratch_bytes);
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_pack(zsc_hip_inflate_plan *pl, const void *d_output, void *d_packed,
+                                                uint64_t packed_cap, void *hip_stream)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    /* the bytes written, whatever the status: what a damaged stream gave is kept */
+    const PkLens lens = {(const uint32_t *)pl->d_res.p, 4u, 1u, PK_NO_STATUS};
+    return pack_enqueue(pl->pack, lens, d_output, d_packed, packed_cap, (hipStream_t)hip_stream);
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_pack_results(zsc_hip_inflate_plan *pl, uint64_t *offsets, uint64_t *total,
+                                                        float *ms)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    return pack_fetch(pl->pack, offsets, total, ms);
+}
+
+namespace {
+/* the device arrays of zsc_hip_unpack calls whose launch may still be running */
+struct UnpackPending {
+    hipEvent_t done;
+    DevBuf table, lens, slots;
+};
+std::mutex g_unpack_mu;
+std::vector<UnpackPending> g_unpack_pending;
+
+void unpack_reap(bool wait)
+{
+    std::lock_guard<std::mutex> lock(g_unpack_mu);
+    for (size_t k = 0; k < g_unpack_pending.size();) {
+        UnpackPending &u = g_unpack_pending[k];
+        if (wait)
+            (void)hipEventSynchronize(u.done);
+        else if (hipEventQuery(u.done) != hipSuccess) {
+            (void)hipGetLastError();
+            k++;
+            continue;
+        }
+        (void)hipEventDestroy(u.done);
+        u.table.release();
+        u.lens.release();
+        u.slots.release();
+        g_unpack_pending[k] = g_unpack_pending.back();
+        g_unpack_pending.pop_back();
+    }
+}
+} // namespace
+
+extern "C" ZlibReturn zsc_hip_unpack(U32 count, const void *d_packed, const uint64_t *packed_offsets, const U32 *lens,
+                                     void *d_dst, const uint64_t *dst_offsets, void *hip_stream)
+{
+    DeviceScope scope;
+    if (zsc_hip_init(-1) != Z_OK)
+        return Z_STREAM_ERROR;
+    unpack_reap(false);
+    if (count == 0)
+        return Z_OK;
+    ZSC_ASSERT(packed_offsets != Z_NULL);
+    ZSC_ASSERT(lens != Z_NULL);
+    ZSC_ASSERT(dst_offsets != Z_NULL);
+    std::vector<uint64_t> table;
+    if (!unpack_table(count, packed_offsets, lens, dst_offsets, table) || ((uintptr_t)d_packed & 15u) ||
+        ((uintptr_t)d_dst & 15u))
+        return Z_STREAM_ERROR;
+    const uint64_t total = table[count];
+    if ((total + PK_TILE - 1u) / PK_TILE > 0x7fffffffull)
+        return Z_MEM_ERROR;
+    if (total == 0)
+        return Z_OK;
+    if (d_packed == Z_NULL || d_dst == Z_NULL)
+        return Z_STREAM_ERROR;
+    UnpackPending u;
+    bool ok = u.table.ensure(8ull * (count + 1ull)) && u.lens.ensure(4ull * count) && u.slots.ensure(8ull * count) &&
+              hipMemcpy(u.table.p, table.data(), 8ull * (count + 1ull), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(u.lens.p, lens, 4ull * count, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(u.slots.p, dst_offsets, 8ull * count, hipMemcpyHostToDevice) == hipSuccess &&
+              hipEventCreate(&u.done) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        u.table.release();
+        u.lens.release();
+        u.slots.release();
+        return Z_MEM_ERROR;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    unpack_enqueue(count, total, d_packed, u.table.p, u.lens.p, d_dst, u.slots.p, st);
+    (void)hipEventRecord(u.done, st);
+    const bool launched = hipGetLastError() == hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(g_unpack_mu);
+        g_unpack_pending.push_back(u);
+    }
+    return launched ? Z_OK : Z_STREAM_ERROR;
+}
+
+extern "C" ZlibReturn zsc_hip_compress_batch_packed(U32 count, const U8 *sources, const uint64_t *source_offsets,
+                                                    U8 *dest, uint64_t dest_cap, uint64_t *dest_offsets,
+                                                    I32 *statuses, I32 level, I32 window_bits, I32 mem_level,
+                                                    ZlibStrategy strategy, U32 align)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(source_offsets != Z_NULL);
+    ZSC_ASSERT(dest_offsets != Z_NULL);
+    if (level == Z_NO_COMPRESSION || !pack_align_ok(align))
+        return Z_STREAM_ERROR;
+    dest_offsets[0] = 0;
+    if (count == 0)
+        return Z_OK;
+    std::vector<U32> lens(count), caps(count);
+    for (U32 i = 0; i < count; i++) {
+        if (source_offsets[i + 1u] < source_offsets[i] || source_offsets[i + 1u] - source_offsets[i] > 0xffffffffull)
+            return Z_STREAM_ERROR;
+        lens[i] = (U32)(source_offsets[i + 1u] - source_offsets[i]);
+    }
+    const uint64_t image = source_offsets[count];
+    ZSC_ASSERT(image == 0 || sources != Z_NULL);
+    std::vector<uint64_t> in_off(count), out_off(count);
+    uint64_t in_bytes = 0, out_bytes = 0;
+    ZlibReturn rc = zsc_hip_deflate_plan_layout(count, lens.data(), level, window_bits, mem_level, in_off.data(),
+                                                out_off.data(), caps.data(), &in_bytes, &out_bytes);
+    if (rc != Z_OK)
+        return rc;
+    zsc_hip_deflate_plan *pl = nullptr;
+    rc = zsc_hip_deflate_plan_create(&pl, count, lens.data(), in_off.data(), out_off.data(), caps.data(), level,
+                                     window_bits, mem_level, strategy);
+    if (rc != Z_OK)
+        return rc;
+    rc = zsc_hip_deflate_plan_pack_enable(pl, align);
+    DevBuf d_img, d_in, d_out, d_packed, d_table, d_lens, d_slots;
+    const uint64_t pcap = std::min(dest_cap, pl->pack.max_total);
+    if (rc == Z_OK &&
+        !(d_img.ensure(image) && d_in.ensure(in_bytes) && d_out.ensure(out_bytes) && d_packed.ensure(pcap) &&
+          d_table.ensure(8ull * (count + 1ull)) && d_lens.ensure(4ull * count) && d_slots.ensure(8ull * count)))
+        rc = Z_MEM_ERROR;
+    /* one copy in, then the image is cut into the plan's layout on the device */
+    if (rc == Z_OK &&
+        !((image == 0 || hipMemcpy(d_img.p, sources + source_offsets[0], image - source_offsets[0],
+                                   hipMemcpyHostToDevice) == hipSuccess) &&
+          hipMemcpy(d_lens.p, lens.data(), 4ull * count, hipMemcpyHostToDevice) == hipSuccess &&
+          hipMemcpy(d_slots.p, in_off.data(), 8ull * count, hipMemcpyHostToDevice) == hipSuccess))
+        rc = Z_STREAM_ERROR;
+    if (rc == Z_OK) {
+        std::vector<uint64_t> table(source_offsets, source_offsets + count + 1u);
+        for (uint64_t &t : table)
+            t -= source_offsets[0];
+        if (hipMemcpy(d_table.p, table.data(), 8ull * (count + 1ull), hipMemcpyHostToDevice) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+        else
+            unpack_enqueue(count, table[count], d_img.p, d_table.p, d_lens.p, d_in.p, d_slots.p, nullptr);
+    }
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_run(pl, d_in.p, d_out.p, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_pack(pl, d_out.p, d_packed.p, pcap, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_results(pl, Z_NULL, statuses);
+    if (rc == Z_OK) {
+        uint64_t total = 0;
+        rc = zsc_hip_deflate_plan_pack_results(pl, dest_offsets, &total, Z_NULL);
+        /* ... and one copy out */
+        if (rc == Z_OK && total && hipMemcpy(dest, d_packed.p, total, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    (void)hipDeviceSynchronize();
+    for (DevBuf *b : {&d_img, &d_in, &d_out, &d_packed, &d_table, &d_lens, &d_slots})
+        b->release();
+    zsc_hip_deflate_plan_destroy(pl);
+    return rc;
+}
+
+extern "C" ZlibReturn zsc_hip_uncompress_batch_packed(U32 count, const U8 *sources, const uint64_t *source_offsets,
+                                                      const U32 *source_lens, const U32 *dest_caps, U8 *dest,
+                                                      uint64_t dest_cap, uint64_t *dest_offsets, U32 *dest_lens,
+                                                      U32 *consumed, I32 *statuses, I32 window_bits, U32 align)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(dest_offsets != Z_NULL);
+    if (!pack_align_ok(align))
+        return Z_STREAM_ERROR;
+    dest_offsets[0] = 0;
+    if (count == 0)
+        return Z_OK;
+    ZSC_ASSERT(source_offsets != Z_NULL);
+    ZSC_ASSERT(source_lens != Z_NULL);
+    ZSC_ASSERT(dest_caps != Z_NULL);
+    if (zsc_hip_init(-1) != Z_OK)
+        return Z_STREAM_ERROR;
+    /* the layout of zsc_hip_uncompress_batch */
+    std::vector<uint64_t> so(count), dof(count), table;
+    uint64_t sb = 0, db = 0;
+    for (U32 i = 0; i < count; i++) {
+        so[i] = sb;
+        dof[i] = db;
+        sb += ((uint64_t)source_lens[i] + 64u + 15u) & ~15ull;
+        db += ((uint64_t)dest_caps[i] + 64u + 15u) & ~15ull;
+    }
+    if (!unpack_table(count, source_offsets, source_lens, so.data(), table))
+        return Z_STREAM_ERROR;
+    const uint64_t first = table[0], image = table[count] - first;
+    for (uint64_t &t : table)
+        t -= first;
+    ZSC_ASSERT(image == 0 || sources != Z_NULL);
+    zsc_hip_inflate_plan *pl = nullptr;
+    ZlibReturn rc = zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_caps, dof.data(), window_bits);
+    if (rc != Z_OK)
+        return rc;
+    rc = zsc_hip_inflate_plan_pack_enable(pl, align);
+    DevBuf d_img, d_src, d_dst, d_packed, d_table, d_lens, d_slots;
+    const uint64_t pcap = std::min(dest_cap, pl->pack.max_total);
+    if (rc == Z_OK &&
+        !(d_img.ensure(image) && d_src.ensure(sb + 64) && d_dst.ensure(db + 64) && d_packed.ensure(pcap) &&
+          d_table.ensure(8ull * (count + 1ull)) && d_lens.ensure(4ull * count) && d_slots.ensure(8ull * count)))
+        rc = Z_MEM_ERROR;
+    if (rc == Z_OK &&
+        !((image == 0 || hipMemcpy(d_img.p, sources + first, image, hipMemcpyHostToDevice) == hipSuccess) &&
+          hipMemcpy(d_table.p, table.data(), 8ull * (count + 1ull), hipMemcpyHostToDevice) == hipSuccess &&
+          hipMemcpy(d_lens.p, source_lens, 4ull * count, hipMemcpyHostToDevice) == hipSuccess &&
+          hipMemcpy(d_slots.p, so.data(), 8ull * count, hipMemcpyHostToDevice) == hipSuccess))
+        rc = Z_STREAM_ERROR;
+    if (rc == Z_OK) {
+        unpack_enqueue(count, image, d_img.p, d_table.p, d_lens.p, d_src.p, d_slots.p, nullptr);
+        rc = zsc_hip_inflate_plan_run(pl, d_src.p, d_dst.p, nullptr);
+    }
+    /* (the results first: a damaged stream that resynchronises is finished there) */
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_results(pl, dest_lens, consumed, statuses, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_pack(pl, d_dst.p, d_packed.p, pcap, nullptr);
+    if (rc == Z_OK) {
+        uint64_t total = 0;
+        rc = zsc_hip_inflate_plan_pack_results(pl, dest_offsets, &total, Z_NULL);
+        if (rc == Z_OK && total && hipMemcpy(dest, d_packed.p, total, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    (void)hipDeviceSynchronize();
+    for (DevBuf *b : {&d_img, &d_src, &d_dst, &d_packed, &d_table, &d_lens, &d_slots})
+        b->release();
+    zsc_hip_inflate_plan_destroy(pl);
+    return rc;
 }
 
 static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
