@@ -373,6 +373,46 @@ ZlibReturn zsc_hip_uncompress_resync_batch(U32 count, const U8 *const *sources, 
  * that decoded cleanly. */
 ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *plan, U32 *errors);
 
+/* Size plans: what dest_caps[i] has to be, found on the device without writing any output
+ * (zsc_amd/csrc/inflate_size.h).  A zlib or raw stream does not carry its length, and a gzip ISIZE is a
+ * number modulo 2^32 at the end of a file not yet trusted; a size plan decodes the streams as a plain
+ * plan does and stores nothing.  source_lens, src_offsets and window_bits as zsc_hip_inflate_plan_create.
+ * dest_limits[i] is the most stream i may inflate to (NULL: 0xFFFFFFFF for every stream).  chunk_bytes
+ * as zsc_hip_inflate_plan_create_chunks (0: the default; below 4 KiB: 4 KiB): a stream longer than that
+ * is sized in pieces, in parallel; 0xFFFFFFFF never cuts a stream.
+ *
+ * The contract.  Status, dest_len and consumed of stream i (_results) are those a plain plan
+ * (zsc_hip_inflate_plan_create) reports with dest_caps[i] = dest_limits[i], for every input, damaged and
+ * truncated ones included: header rules, invalid code sets and symbols, a distance beyond the output so
+ * far or beyond the header's window, truncation (Z_BUF_ERROR), Z_NEED_DICT, data errors survived through
+ * inflateSync (Z_DATA_ERROR, zsc_hip_inflate_plan_data_errors) and a gzip ISIZE that is not the length
+ * are all found.  A stream longer than its limit is Z_BUF_ERROR with dest_len equal to the limit, as the
+ * plain plan gives it: the limit is a guard against decompression bombs.
+ *   The one exception: the check value in a zlib or gzip trailer is not compared, because there are no
+ *   bytes to take it over.  A stream whose only fault is its Adler-32 or CRC-32 is reported Z_OK with
+ *   its full length, and consumed is the trailer's end; inflating it afterwards reports the fault.
+ *   (Where a data error has been survived, the salvaged output cannot match the writer's check value, and
+ *   the check is taken as failed, as a plain plan finds it.)
+ *
+ * _run (d_dst is ignored and may be NULL: nothing is ever written through it), _results, _destroy,
+ * zsc_hip_inflate_plan_sections (the pieces a stream was sized in, in parallel, or 0),
+ * zsc_hip_inflate_plan_data_errors and zsc_hip_inflate_plan_scratch_bytes work on it;
+ * zsc_hip_inflate_plan_pack_enable and zsc_hip_inflate_plan_index_enable return Z_STREAM_ERROR.  As with
+ * chunks plans the parallel path only ever reports a clean Z_OK; a stream it cannot finish -- a broken
+ * chain, a reach before the output or beyond the header's window, the 4 * source_len + 64 KiB work
+ * bound, a total above the limit, an ISIZE mismatch, any error -- is sized by the whole-stream decode
+ * from its start.  Scratch: 64 bytes per chunk of the streams longer than chunk_bytes (32 bytes of
+ * candidates, 32 bytes of records; no ring and no window), 8 bytes per chunk after a stream's first, and
+ * 96 bytes per stream plus 16.  A plan of any other kind allocates, launches and returns what it did
+ * without size plans. */
+ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **plan, U32 count,
+                                            const U32 *source_lens, const uint64_t *src_offsets,
+                                            const U32 *dest_limits, I32 window_bits, U32 chunk_bytes);
+/* host-pointer batch through a size plan (default chunk_bytes).  dest_lens: in, the limits; out, the
+ * sizes.  source_lens: out, the bytes consumed.  statuses may be NULL. */
+ZlibReturn zsc_hip_uncompress_sizes_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                          U32 *dest_lens, I32 *statuses, I32 window_bits);
+
 /* seek-point indexes -------------------------------------------------------- */
 
 /* A chunks plan finds, on every run, where the chained pieces of a stream start, how long each one's

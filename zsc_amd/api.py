@@ -111,6 +111,9 @@ def _load() -> C.CDLL:
     L.zsc_hip_inflate_plan_create_resync.argtypes = L.zsc_hip_inflate_plan_create_sections.argtypes
     L.zsc_hip_uncompress_resync_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes
     L.zsc_hip_inflate_plan_data_errors.argtypes = [C.c_void_p, u32p]
+    L.zsc_hip_inflate_plan_create_size.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p, C.c_int32,
+                                                   C.c_uint32]
+    L.zsc_hip_uncompress_sizes_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u32p, u32p, i32p, C.c_int32]
     L.zsc_hip_index_validate.argtypes = [C.c_char_p, C.c_uint64]
     L.zsc_hip_index_info.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(IndexHeader)]
     L.zsc_hip_index_range.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, u32p, u32p, u32p, u32p]
@@ -405,6 +408,39 @@ def uncompress_resync_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
     return _uncompress_batch(lib.zsc_hip_uncompress_resync_batch, sources, dest_caps, window_bits)
 
 
+NO_LIMIT = 0xFFFFFFFF
+
+
+def uncompress_sizes_batch(sources: Sequence[bytes], limits: Sequence[int] | None = None,
+                           window_bits: int = DEF_WBITS) -> Tuple[int, List[int], List[int], List[int]]:
+    """zsc_hip_uncompress_sizes_batch: what every stream inflates to, found on the device without writing
+    any output.  limits[i] is the most stream i may inflate to (None: no limit); a stream longer than its
+    limit is Z_BUF_ERROR with its size equal to the limit.  Status, size and consumed are uncompress_batch's
+    with dest_caps = limits, except that the check value of a zlib / gzip trailer is not compared.
+    Returns (rc, sizes, consumed, statuses)."""
+    count = len(sources)
+    srcs = (C.c_char_p * count)(*sources)
+    slen = (C.c_uint32 * count)(*[len(s) for s in sources])
+    dlen = (C.c_uint32 * count)(*([NO_LIMIT] * count if limits is None else limits))
+    stat = (C.c_int32 * count)()
+    rc = lib.zsc_hip_uncompress_sizes_batch(count, srcs, slen, dlen, stat, window_bits)
+    return rc, list(dlen) if rc == Z_OK else [], list(slen), list(stat)
+
+
+def uncompress_batch_auto(sources: Sequence[bytes], window_bits: int = DEF_WBITS, limit: int | None = None):
+    """Inflate streams of unknown length: size them (uncompress_sizes_batch, every stream under `limit`
+    if one is given), then run uncompress_chunks_batch with dest_caps[i] set to the reported size, so no
+    byte of capacity is allocated beyond it.  Returns what that call returns and the sizes:
+    (rc, outputs, consumed, statuses, sizes).  The statuses are the inflate's: a stream cut off at the
+    limit comes back Z_BUF_ERROR with `limit` bytes, one whose check value is wrong Z_DATA_ERROR."""
+    count = len(sources)
+    rc, sizes, _, _ = uncompress_sizes_batch(sources, None if limit is None else [limit] * count, window_bits)
+    if rc != Z_OK:
+        return rc, [], [], [], []
+    rc, outs, used, stat = uncompress_chunks_batch(sources, sizes, window_bits)
+    return rc, outs, used, stat, sizes
+
+
 def uncompress_indexed_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
                              indexes: Sequence[Optional[bytes]], window_bits: int = DEF_WBITS):
     """zsc_hip_uncompress_indexed_batch: as uncompress_batch, with every stream that has a valid index
@@ -650,16 +686,26 @@ class InflatePlan(_Packing):
     length) or None, ...] decodes only the whole pieces that cover that range of the stream's output
     (index_range), to the start of the stream's destination.  src_offsets=[...] (multiples of 16) puts the
     streams where the caller has them instead of one behind the other -- the offsets of an image packed with
-    align 16 or more, say, which then is the plan's input as it lies; src_bytes is not meaningful then."""
+    align 16 or more, say, which then is the plan's input as it lies; src_bytes is not meaningful then.
+    size_only=True makes a size plan (zsc_hip_inflate_plan_create_size): dest_caps are the limits (None: no
+    limit), nothing is written, run() takes d_dst 0, and results() gives the sizes; a stream longer than
+    chunk_bytes is sized in parallel pieces (chunk_bytes 0 = the default, NO_LIMIT = never cut a stream)."""
     _pack_kind = "inflate"
 
-    def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int],
+    def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int] | None,
                  window_bits: int = DEF_WBITS, decode_order: Sequence[int] | None = None,
                  sections: bool = False, chunks: bool = False, chunk_bytes: int = 0, resync: bool = False,
                  keep_index: bool = False, indexes: Sequence[Optional[bytes]] | None = None,
                  ranges: Sequence[Optional[Tuple[int, int]]] | None = None,
-                 src_offsets: Sequence[int] | None = None):
+                 src_offsets: Sequence[int] | None = None, size_only: bool = False):
         self.count = n = len(source_lens)
+        if size_only:
+            if sections or chunks or resync or keep_index or indexes is not None or decode_order is not None:
+                raise ValueError("a size plan is no other kind of plan and takes no decode_order")
+            if dest_caps is None:
+                dest_caps = [NO_LIMIT] * n
+        elif dest_caps is None:
+            raise ValueError("dest_caps are needed")
         if keep_index and not chunks:
             raise ValueError("keep_index needs a chunks plan")
         if ranges is not None and indexes is None:
@@ -671,7 +717,7 @@ class InflatePlan(_Packing):
             so.append(sb)
             do.append(db)
             sb += (sl + 64 + 15) & ~15
-            db += (dc + 64 + 15) & ~15
+            db += 0 if size_only else (dc + 64 + 15) & ~15
         if src_offsets is not None:
             if len(src_offsets) != n:
                 raise ValueError("one source offset per stream")
@@ -684,7 +730,11 @@ class InflatePlan(_Packing):
             raise ValueError("a resync plan is a sections plan, not a chunks plan")
         if sections and chunks:
             raise ValueError("a plan is a sections plan or a chunks plan, not both")
-        if indexes is not None:
+        if size_only:
+            rc = lib.zsc_hip_inflate_plan_create_size(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
+                                                      (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
+                                                      window_bits, chunk_bytes)
+        elif indexes is not None:
             if len(indexes) != n or (ranges is not None and len(ranges) != n):
                 raise ValueError("one index (and one range) per stream")
             blobs = (C.c_char_p * n)(*indexes)
@@ -735,7 +785,7 @@ class InflatePlan(_Packing):
             raise RuntimeError(f"zsc_hip_inflate_plan_index_export failed: {rc}")
         return buf.raw[:got.value]
 
-    def run(self, d_src: int, d_dst: int, stream: int = 0) -> None:
+    def run(self, d_src: int, d_dst: int = 0, stream: int = 0) -> None:
         rc = lib.zsc_hip_inflate_plan_run(self._h, C.c_void_p(d_src), C.c_void_p(d_dst),
                                           C.c_void_p(stream))
         if rc != Z_OK:

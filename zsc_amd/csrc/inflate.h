@@ -295,6 +295,14 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
 /* resync variants (inflate_resync.h), with si pointing to an InfSecErr:
  *   INF_SEC_ERRSTATE record the error state inflateSync would start from (InfSecErr) */
 #define INF_SEC_ERRSTATE 64u
+/* the size variant (inflate_size.h), together with INF_SEC_COUNT:
+ *   INF_SEC_SIZE     the whole stream as SEC = 0 decodes it -- wrapper, trailer, ISIZE, results to res / rs,
+ *                    a data error re-entered through rs -- with nothing stored (INF_SEC_COUNT) and no check
+ *                    value of the output: the trailer's Adler-32 / CRC-32 is not compared, except that
+ *                    after a survived data error it is taken as failed (the salvaged output cannot match it).
+ * INF_SEC_BITSTART | INF_SEC_COUNT is the piece variant of the same path: a piece's length, link, reach,
+ * longest distance and end bit with no ring and no window. */
+#define INF_SEC_SIZE 128u
 #define INF_WIN 32768u   /* window entries: win[INF_WIN - d] is the byte d before the piece */
 #define INF_PH 0x8000u   /* a placeholder symbol of the 16-bit output */
 #define INF_PC_CANDS 4u  /* candidates per chunk */
@@ -351,7 +359,10 @@ template <uint32_t SEC = 0u>
 DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume *rs, InfSecInfo *si = nullptr,
                       InfPiece *pc = nullptr)
 {
-    constexpr bool PIECE_OUT = (SEC & (INF_SEC_SYM16 | INF_SEC_EXTWIN)) != 0u;
+    constexpr bool PIECE_OUT = (SEC & (INF_SEC_SYM16 | INF_SEC_EXTWIN)) != 0u ||
+                               (SEC & (INF_SEC_BITSTART | INF_SEC_COUNT)) == (INF_SEC_BITSTART | INF_SEC_COUNT);
+    constexpr bool SIZE_ONLY = (SEC & INF_SEC_SIZE) != 0u;
+    constexpr bool SECTION = SEC != 0u && !SIZE_ONLY; /* results go to *si (and *pc) */
     const uint8_t *src = job.src;
     const uint32_t n = job.n, cap = job.cap;
     uint8_t *dst = job.dst;
@@ -375,7 +386,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     LANEVAR(uint32_t, cur); /* dword GLANE of the current 256-byte input chunk */
     FOR_GLANES { LV(cur) = inf_input_dword(src, 4u * (uint32_t)GLANE, n); }
 
-    const int resumed = SEC == 0u && GUNI(rs->state) == 1u;
+    const int resumed = !SECTION && GUNI(rs->state) == 1u;
     uint32_t pos = 0; /* output bytes produced (each is stored to dst as it is made) */
     uint32_t dmax = 32768u;
     int gzip = 0;
@@ -1115,6 +1126,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
             uint32_t v;
             INF_NEED(32);
             INF_TAKE(v, 32);
+            if constexpr (SIZE_ONLY) {
+                if ((wrap & 4) && data_errors)
+                    INF_BADX(32, 32); /* (the check value of an output with a hole in it) */
+            } else
             if (wrap & 4) {
 #ifndef ZSC_WAVE_EMU
                 __threadfence_block();
@@ -1136,7 +1151,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     }
 
 bad:
-    if constexpr (SEC != 0u) {
+    if constexpr (SECTION) {
         ON_GLANE0
         {
             if constexpr ((SEC & INF_SEC_BITSTART) != 0u) {
@@ -1177,7 +1192,7 @@ bad:
     return 1;
 
 done:
-    if constexpr (SEC != 0u) {
+    if constexpr (SECTION) {
         ON_GLANE0
         {
             if constexpr ((SEC & INF_SEC_BITSTART) != 0u) {

@@ -344,7 +344,9 @@ DEV void chk_scan(const IchkPlan &P, const uint8_t *src_all, uint32_t t)
 #define ZSC_GROUP INF_GROUP
 #include "wave_group.h"
 
-/* the piece context for chunk k's candidate at bit offset `bit` */
+/* the piece context for chunk k's candidate at bit offset `bit` (SIZE: a size plan, inflate_size.h, which
+ * has no rings) */
+template <bool SIZE = false>
 DEV void chk_piece(const IchkPlan &P, uint32_t cb, uint32_t k, uint32_t nchunks, uint64_t bit, InfPiece *pc,
                    const uint8_t *win)
 {
@@ -353,6 +355,9 @@ DEV void chk_piece(const IchkPlan &P, uint32_t cb, uint32_t k, uint32_t nchunks,
         pc->base_bit = bit & ~7ull;
         pc->chunk_bits = (uint64_t)P.chunk_bytes * 8u;
         pc->cand = P.cand + (uint64_t)cb * INF_PC_CANDS;
+        if constexpr (SIZE)
+            pc->ring = nullptr;
+        else
         pc->ring = P.ring + (uint64_t)(cb + k) * INF_WIN;
         pc->win = win;
         pc->skip = (uint32_t)(bit & 7u);
@@ -363,7 +368,9 @@ DEV void chk_piece(const IchkPlan &P, uint32_t cb, uint32_t k, uint32_t nchunks,
 }
 
 /* decode chunk k of stream s from candidate j0 on (only j0 if `single`) until one ends cleanly, and
- * record the outcome in the chunk's records (its ring holds the tail) */
+ * record the outcome in the chunk's records (its ring holds the tail; SIZE: the piece is only counted,
+ * and there is no ring) */
+template <bool SIZE = false>
 DEV void chk_count_chunk(const IchkPlan &P, const uint8_t *src_all, InfLds *lds, InfSecInfo *si, InfPiece *pc,
                          uint32_t s, uint32_t k, uint32_t j0, int single)
 {
@@ -382,13 +389,16 @@ DEV void chk_count_chunk(const IchkPlan &P, const uint8_t *src_all, InfLds *lds,
         if (bit == INF_PC_NONE)
             break;
         const uint32_t start = (uint32_t)(bit >> 3);
-        chk_piece(P, cb, k, nch, bit, pc, nullptr);
+        chk_piece<SIZE>(P, cb, k, nch, bit, pc, nullptr);
         InfJob job;
         job.src = src_all + it->src_off + start;
         job.n = n - start;
         job.dst = nullptr;
         job.cap = GUNI(it->dst_cap);
         job.window_bits = k == 0u ? P.sp.window_bits : -15;
+        if constexpr (SIZE)
+            inflate_stream<INF_SEC_BITSTART | INF_SEC_COUNT | INF_SEC_NOTRAIL>(job, lds, nullptr, nullptr, si, pc);
+        else
         inflate_stream<INF_SEC_BITSTART | INF_SEC_SYM16 | INF_SEC_NOTRAIL>(job, lds, nullptr, nullptr, si, pc);
         const uint32_t outcome = GUNI(si->outcome);
         ON_GLANE0 { SEC_ADD(&S->work, (unsigned long long)GUNI(si->stop)); }
@@ -422,7 +432,7 @@ DEV void chk_count_chunk(const IchkPlan &P, const uint8_t *src_all, InfLds *lds,
 /* step 3: a group takes chunks until the queue is empty, and tries each one's candidates in order
  * (RETRY: only the wanted candidate of the chunks that have one).  A stream in whose later chunks the
  * scan found no candidate at all cannot be split: it goes to the serial decoder at once. */
-template <bool RETRY = false>
+template <bool RETRY = false, bool SIZE = false>
 DEV void chk_count_worker(const IchkPlan &P, const uint8_t *src_all, InfLds *lds, InfSecInfo *si, InfPiece *pc)
 {
     uint32_t s, k;
@@ -435,7 +445,7 @@ DEV void chk_count_worker(const IchkPlan &P, const uint8_t *src_all, InfLds *lds
         const uint32_t wanted = RETRY ? GUNI(P.want[GUNI(S->base) + k]) : 0u;
         if (RETRY && wanted == CHK_USED_NONE)
             continue;
-        chk_count_chunk(P, src_all, lds, si, pc, s, k, wanted, RETRY);
+        chk_count_chunk<SIZE>(P, src_all, lds, si, pc, s, k, wanted, RETRY);
     }
 }
 
@@ -444,6 +454,7 @@ DEV void chk_count_worker(const IchkPlan &P, const uint8_t *src_all, InfLds *lds
  * too -- the group decodes the entered candidate here and goes on, so no run of such chunks breaks the
  * chain.  A chain of one piece is left to the serial decoder: nothing runs in parallel, and the
  * write pass would decode it once more at the serial rate. */
+template <bool SIZE = false>
 DEV void chk_resolve(const IchkPlan &P, const uint8_t *src_all, InfLds *lds, InfSecInfo *si, InfPiece *pc, uint32_t a)
 {
     const uint32_t s = GUNI(P.sp.active[a]);
@@ -457,7 +468,7 @@ DEV void chk_resolve(const IchkPlan &P, const uint8_t *src_all, InfLds *lds, Inf
     uint64_t sum = 0;
     for (;;) {
         if (GUNI(P.cused[cb + k]) != j)
-            chk_count_chunk(P, src_all, lds, si, pc, s, k, j, 1);
+            chk_count_chunk<SIZE>(P, src_all, lds, si, pc, s, k, j, 1);
         if (GUNI(P.cused[cb + k]) != j)
             break; /* (the entered candidate did not end cleanly, or the work bound was reached) */
         const uint32_t link = GUNI(P.sp.clink[cb + k]), len = GUNI(P.sp.clen[cb + k]);

@@ -30,6 +30,7 @@
 #include "inflate_chunks.h"
 #include "inflate_resync.h"
 #include "inflate_index.h"
+#include "inflate_size.h"
 #include "deflate_index.h"
 #include "deflate_verify.h"
 #include "pack.h"
@@ -956,6 +957,93 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU
     if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
         lds_all[grp].cktab = crc_table;
     idx_write_worker(P, src, dst, &lds_all[grp], &info[grp], &piece[grp], res, resume);
+}
+
+/* kernel 10 (inflate_size.h): the output lengths of the streams, nothing stored.  k_inflate_size is
+ * k_inflate's launch over the size decode; ahead of it a size plan with chunks runs k_chk_setup, k_chk_scan
+ * and k_chk_want unchanged and these over the piece count variant */
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_inflate_size(
+    const uint8_t *__restrict__ src, const ZdInfItem *__restrict__ items, const uint32_t *__restrict__ order,
+    InfResult *__restrict__ res, InfResume *__restrict__ resume, uint32_t *__restrict__ pending, int32_t window_bits,
+    uint32_t count)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256]; /* (the header CRC of a gzip member is over input bytes: it stays) */
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    InfLds *lds = &lds_all[grp];
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds->cktab = crc_table;
+    /* one queue, as k_inflate (pending[1]; longest input first) */
+    for (;;) {
+        uint32_t slot = 0;
+        if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+            slot = atomicAdd(pending + 1, 1u);
+        slot = (uint32_t)__shfl((int)slot, (int)(threadIdx.x & (64u - INF_GROUP)));
+        if (slot >= count)
+            break;
+        const uint32_t i = order[slot];
+        if (resume[i].state == 2u)
+            continue; /* finished by the chunked path, or in an earlier launch */
+        const ZdInfItem it = items[i];
+        InfJob job;
+        job.src = src + it.src_off;
+        job.n = it.src_len;
+        job.dst = nullptr;
+        job.cap = it.dst_cap; /* the limit */
+        job.window_bits = window_bits;
+        if (size_stream(job, lds, &res[i], &resume[i])) {
+            if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+                atomicAdd(pending, 1u); /* the host launches once more for these */
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_size_count(
+    const uint8_t *__restrict__ src, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    chk_count_worker<false, true>(P, src, &lds_all[grp], &info[grp], &piece[grp]);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_size_retry(
+    const uint8_t *__restrict__ src, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    chk_count_worker<true, true>(P, src, &lds_all[grp], &info[grp], &piece[grp]);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_size_resolve(
+    const uint8_t *__restrict__ src, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + grp; a < P.nactive; a += gridDim.x * INF_PER_WAVE)
+        chk_resolve<true>(P, src, &lds_all[grp], &info[grp], &piece[grp], a);
+}
+
+__global__ __launch_bounds__(64) void k_size_finish(const uint8_t *__restrict__ src, IchkPlan P,
+                                                    InfResult *__restrict__ res, InfResume *__restrict__ resume)
+{
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < P.nactive;
+         a += gridDim.x * INF_PER_WAVE)
+        size_finish(P, src, res, resume, a);
 }
 
 /* the export of a chunks plan's index: the records of stream s's chain, each window's place in the
@@ -3409,6 +3497,9 @@ struct zsc_hip_inflate_plan {
     DevBuf d_cerr, d_chain_fl, d_rst;
     /* indexed plans only (inflate_index.h; they also use d_sitems, d_sst, d_active, d_q, d_nsec, d_clen,
      * d_chain_k, d_chain_ck, d_cand and d_win) */
+    /* size plans only (inflate_size.h; with chunks they use cp and the chunks plan's record buffers, never
+     * d_ring, d_win or d_chain_ck) */
+    bool size_only = false, size_ran = false;
     bool indexed = false, idx_fixed = false;
     IidxPlan ip = {};
     uint32_t idx_active = 0;
@@ -3695,6 +3786,109 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_chunks(zsc_hip_inflate_plan **
     return Z_OK;
 }
 
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                       const U32 *source_lens, const uint64_t *src_offsets,
+                                                       const U32 *dest_limits, I32 window_bits, U32 chunk_bytes)
+{
+    ZSC_ASSERT(plan_out != Z_NULL);
+    *plan_out = nullptr;
+    /* a plain plan's items with the limits for capacities and no destination; the queue hands out the
+     * longest inputs first (the capacities, all alike by default, say nothing about the decoding time) */
+    std::vector<U32> limits(count), order(count);
+    std::vector<uint64_t> dof(count, 0);
+    for (U32 i = 0; i < count; i++) {
+        limits[i] = dest_limits ? dest_limits[i] : 0xffffffffu;
+        order[i] = i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](U32 a, U32 b) { return source_lens[a] > source_lens[b]; });
+    ZlibReturn rc = zsc_hip_inflate_plan_create_ordered(plan_out, count, source_lens, src_offsets, limits.data(),
+                                                        dof.data(), window_bits, order.data());
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    zsc_hip_inflate_plan *pl = *plan_out;
+    pl->size_only = true;
+    const uint32_t cb = chunk_bytes == 0 ? CHK_DEFAULT_BYTES : std::max<uint32_t>(chunk_bytes, CHK_MIN_BYTES);
+    /* per stream longer than a chunk: its chunks; the scan visits every chunk but the first (any limit
+     * will do: a piece is only counted, no position inside it is ever signed) */
+    std::vector<IsecItem> items(count);
+    std::vector<IsecTile> scan;
+    std::vector<uint32_t> active;
+    uint64_t nchunks = 0;
+    for (U32 i = 0; i < count; i++) {
+        IsecItem &it = items[i];
+        it.src_off = src_offsets[i];
+        it.dst_off = 0;
+        it.src_len = source_lens[i];
+        it.dst_cap = limits[i];
+        it.cap = 0;
+        it.tile0 = (uint32_t)nchunks;
+        it.ntiles = 0;
+        it.pad = 0;
+        if (chunk_bytes != 0xffffffffu && source_lens[i] > cb) {
+            it.ntiles = (uint32_t)(((uint64_t)source_lens[i] + cb - 1u) / cb);
+            for (uint32_t k = 1; k < it.ntiles; k++)
+                scan.push_back(IsecTile{i, k});
+            active.push_back(i);
+            nchunks += it.ntiles;
+        }
+    }
+    if (nchunks >= 0x03ffffffull) { /* (links hold chunk * 4 + candidate in 28 bits) */
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    const uint64_t nt = std::max<uint64_t>(1, scan.size()), nc = std::max<uint64_t>(1, count);
+    const uint64_t ch = std::max<uint64_t>(1, nchunks);
+    /* the candidates and the records of a chunk; no ring, no window, no slice check values */
+    bool ok = pl->d_sitems.ensure(sizeof(IsecItem) * nc) && pl->d_tiles.ensure(sizeof(IsecTile) * nt) &&
+              pl->d_nsec.ensure(4 * nc) && pl->d_sst.ensure(sizeof(IsecStream) * nc) && pl->d_active.ensure(4 * nc) &&
+              pl->d_q.ensure(16) && pl->d_cstop.ensure(4 * ch) && pl->d_clink.ensure(4 * ch) &&
+              pl->d_clen.ensure(4 * ch) && pl->d_chain_k.ensure(4 * ch) && pl->d_chain_off.ensure(4 * ch) &&
+              pl->d_cand.ensure(8ull * INF_PC_CANDS * ch) && pl->d_cused.ensure(4 * ch) &&
+              pl->d_creach.ensure(4 * ch) && pl->d_want.ensure(4 * ch);
+    if (ok && count)
+        ok = hipMemcpy(pl->d_sitems.p, items.data(), sizeof(IsecItem) * count, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !scan.empty())
+        ok = hipMemcpy(pl->d_tiles.p, scan.data(), sizeof(IsecTile) * scan.size(), hipMemcpyHostToDevice) ==
+             hipSuccess;
+    if (ok && !active.empty())
+        ok = hipMemcpy(pl->d_active.p, active.data(), 4 * active.size(), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        zsc_hip_inflate_plan_destroy(pl);
+        *plan_out = nullptr;
+        return Z_MEM_ERROR;
+    }
+    IchkPlan &P = pl->cp;
+    P.sp.items = (const IsecItem *)pl->d_sitems.p;
+    P.sp.tiles = (const IsecTile *)pl->d_tiles.p;
+    P.sp.nsec = (uint32_t *)pl->d_nsec.p;
+    P.sp.st = (IsecStream *)pl->d_sst.p;
+    P.sp.active = (uint32_t *)pl->d_active.p;
+    P.sp.q = (uint32_t *)pl->d_q.p;
+    P.sp.cstop = (uint32_t *)pl->d_cstop.p;
+    P.sp.clink = (uint32_t *)pl->d_clink.p;
+    P.sp.clen = (uint32_t *)pl->d_clen.p;
+    P.sp.chain_k = (uint32_t *)pl->d_chain_k.p;
+    P.sp.chain_off = (uint32_t *)pl->d_chain_off.p;
+    P.sp.count = count;
+    P.sp.ntiles = (uint32_t)scan.size();
+    P.sp.pool = (uint32_t)nchunks;
+    P.sp.window_bits = window_bits;
+    P.sp.work_mul = SEC_WORK_MUL;
+    P.sp.work_add = SEC_WORK_ADD;
+    P.cand = (uint64_t *)pl->d_cand.p;
+    P.cused = (uint32_t *)pl->d_cused.p;
+    P.creach = (uint32_t *)pl->d_creach.p;
+    P.want = (uint32_t *)pl->d_want.p;
+    P.nactive = (uint32_t)active.size();
+    P.chunk_bytes = cb;
+    pl->ncand_total = nchunks;
+    pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
+                        (8ull * INF_PC_CANDS + 32) * ch;
+    return Z_OK;
+}
+
 extern "C" ZlibReturn zsc_hip_inflate_plan_create_resync(zsc_hip_inflate_plan **plan_out, U32 count,
                                                          const U32 *source_lens, const uint64_t *src_offsets,
                                                          const U32 *dest_caps, const uint64_t *dst_offsets,
@@ -3875,6 +4069,35 @@ static void chk_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst
                        (const uint8_t *)d_src, P.sp, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
 }
 
+/* the launches of a size plan's chunked path, ahead of k_inflate_size (none when no stream is longer
+ * than a chunk): the chunks plan's without the window and write passes */
+static void size_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, hipStream_t st)
+{
+    const IchkPlan &P = pl->cp;
+    if (P.nactive == 0)
+        return;
+    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
+    const uint32_t per_stream = std::max(1u, std::min(P.nactive, fill));
+    const uint32_t per_group = (per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE;
+    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
+    const uint32_t scans = std::max(1u, std::min(P.sp.ntiles, fill * 4u));
+    hipLaunchKernelGGL(k_chk_setup, dim3(per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_chk_scan, dim3(scans), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_size_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_chk_want, dim3(per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_size_retry, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_size_resolve, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P);
+    hipLaunchKernelGGL(k_size_finish, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P,
+                       (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+}
+
+static void size_launch(zsc_hip_inflate_plan *pl, const void *d_src, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_inflate_size, dim3(inflate_grid(pl->count)), dim3(64), 0, st, (const uint8_t *)d_src,
+                       (const ZdInfItem *)pl->d_items.p, (const uint32_t *)pl->d_order.p, (InfResult *)pl->d_res.p,
+                       (InfResume *)pl->d_resume.p, (uint32_t *)pl->d_pending.p, pl->window_bits, pl->count);
+}
+
 /* the launches of a resync plan, ahead of k_inflate: the sections plan's scan and setup, then its own */
 static void rsy_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
 {
@@ -3936,6 +4159,20 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
         HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
     }
+    if (pl->size_only) {
+        /* nothing is written through d_dst: it is not looked at */
+        pl->last_dst = nullptr;
+        pl->size_ran = true;
+        HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+        HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
+        (void)hipEventRecord(pl->ev0, st);
+        size_enqueue(pl, d_src, st);
+        size_launch(pl, d_src, st);
+        (void)hipEventRecord(pl->ev1, st);
+        pl->timed = true;
+        HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
+        return Z_OK;
+    }
     (void)hipEventRecord(pl->ev0, st);
     if (pl->resync)
         rsy_enqueue(pl, d_src, d_dst, st);
@@ -3967,12 +4204,17 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_results(zsc_hip_inflate_plan *pl, U32
     /* streams that hit a data error and found a flush marker behind it (inflateSync) are
      * inflated again from there, as zsc_uncompress's loop does (src/zsc_uncompr.c:104-125);
      * every round consumes at least the marker, so this ends */
-    for (uint32_t round = 0; pl->count && pl->last_dst; round++) {
+    for (uint32_t round = 0; pl->count && (pl->last_dst || pl->size_ran); round++) {
         uint32_t pending = 0;
         HIP_TRY(hipMemcpy(&pending, pl->d_pending.p, 4, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
         if (pending == 0 || round > (1u << 30))
             break;
         HIP_TRY(hipMemsetAsync(pl->d_pending.p, 0, 8, pl->last_stream), return Z_STREAM_ERROR);
+        if (pl->size_only) {
+            size_launch(pl, pl->last_src, pl->last_stream);
+            HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+            continue;
+        }
         hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, pl->last_stream,
                            (const uint8_t *)pl->last_src, (uint8_t *)pl->last_dst,
                            (const ZdInfItem *)pl->d_items.p, (const uint32_t *)pl->d_order.p,
@@ -4025,7 +4267,8 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U3
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     ZSC_ASSERT(sections != Z_NULL);
-    if (!(pl->sections || pl->chunks || pl->indexed) || !pl->last_dst || pl->count == 0) {
+    if (!(pl->sections || pl->chunks || pl->indexed || pl->size_only) || !(pl->last_dst || pl->size_ran) ||
+        pl->count == 0) {
         for (uint32_t i = 0; i < pl->count; i++)
             sections[i] = 0;
         return Z_OK;
@@ -4040,7 +4283,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *pl,
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     ZSC_ASSERT(errors != Z_NULL);
-    if (!pl->last_dst || pl->count == 0) {
+    if (!(pl->last_dst || pl->size_ran) || pl->count == 0) {
         for (uint32_t i = 0; i < pl->count; i++)
             errors[i] = 0;
         return Z_OK;
@@ -4254,13 +4497,63 @@ extern "C" ZlibReturn zsc_hip_uncompress_indexed_batch(U32 count, const U8 *cons
                                  index_lens);
 }
 
+/* host-pointer batch through a size plan (default chunk_bytes): the sources staged in one device buffer */
+extern "C" ZlibReturn zsc_hip_uncompress_sizes_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                                     U32 *dest_lens, I32 *statuses, I32 window_bits)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(sources != Z_NULL);
+    ZSC_ASSERT(source_lens != Z_NULL);
+    ZSC_ASSERT(dest_lens != Z_NULL);
+    if (count == 0)
+        return Z_OK;
+    if (zsc_hip_init(-1) != Z_OK)
+        return Z_STREAM_ERROR;
+    std::vector<uint64_t> so(count);
+    uint64_t sb = 0;
+    for (U32 i = 0; i < count; i++) {
+        so[i] = sb;
+        sb += ((uint64_t)source_lens[i] + 64u + 15u) & ~15ull;
+    }
+    zsc_hip_inflate_plan *pl = nullptr;
+    ZlibReturn rc = zsc_hip_inflate_plan_create_size(&pl, count, source_lens, so.data(), dest_lens, window_bits, 0);
+    if (rc != Z_OK)
+        return rc;
+    DevBuf d_src;
+    if (!d_src.ensure(sb + 64)) {
+        zsc_hip_inflate_plan_destroy(pl);
+        return Z_MEM_ERROR;
+    }
+    for (U32 i = 0; i < count && rc == Z_OK; i++) {
+        ZSC_ASSERT(sources[i] != Z_NULL);
+        if (source_lens[i] && hipMemcpy((uint8_t *)d_src.p + so[i], sources[i], source_lens[i],
+                                        hipMemcpyHostToDevice) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    std::vector<U32> outl(count), used(count);
+    std::vector<I32> stat(count);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_run(pl, d_src.p, nullptr, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_results(pl, outl.data(), used.data(), stat.data(), nullptr);
+    for (U32 i = 0; i < count && rc == Z_OK; i++) {
+        dest_lens[i] = outl[i];
+        source_lens[i] = used[i];
+        if (statuses)
+            statuses[i] = stat[i];
+    }
+    d_src.release();
+    zsc_hip_inflate_plan_destroy(pl);
+    return rc;
+}
+
 /* ---- packing an inflate plan's outputs, unpacking, and the host images (pack.h) ----------------- */
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_pack_enable(zsc_hip_inflate_plan *pl, U32 align)
 {
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
-    if (!pack_align_ok(align))
+    if (!pack_align_ok(align) || pl->size_only) /* (a size plan has no outputs to pack) */
         return Z_STREAM_ERROR;
     if (pl->pack.on) {
         pack_set_align(pl->pack, align);
