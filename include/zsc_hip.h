@@ -392,7 +392,8 @@ ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *plan, U32 *err
  *   bytes to take it over.  A stream whose only fault is its Adler-32 or CRC-32 is reported Z_OK with
  *   its full length, and consumed is the trailer's end; inflating it afterwards reports the fault.
  *   (Where a data error has been survived, the salvaged output cannot match the writer's check value, and
- *   the check is taken as failed, as a plain plan finds it.)
+ *   the check is taken as failed, as a plain plan finds it.)  A check plan (below) compares the check value
+ *   too, and hands it out.
  *
  * _run (d_dst is ignored and may be NULL: nothing is ever written through it), _results, _destroy,
  * zsc_hip_inflate_plan_sections (the pieces a stream was sized in, in parallel, or 0),
@@ -412,6 +413,47 @@ ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **plan, U32 cou
  * sizes.  source_lens: out, the bytes consumed.  statuses may be NULL. */
 ZlibReturn zsc_hip_uncompress_sizes_batch(U32 count, const U8 *const *sources, U32 *source_lens,
                                           U32 *dest_lens, I32 *statuses, I32 window_bits);
+
+/* Check plans: "is this archive intact?" answered on the device without writing any output
+ * (zsc_amd/csrc/inflate_check.h) -- gzip -t for a batch.  A check plan decodes the streams as a plain plan
+ * does, keeps only the last window of each output in a 64 KiB ring owned by the lane group that decodes it,
+ * and folds the output into the running Adler-32 / CRC-32 before the ring wraps over it.  Arguments as
+ * zsc_hip_inflate_plan_create_size: dest_limits[i] is the most stream i may inflate to (NULL: 0xFFFFFFFF
+ * for every stream), a stream longer than chunk_bytes is checked in pieces, in parallel (0: the default;
+ * below 4 KiB: 4 KiB; 0xFFFFFFFF never cuts a stream).
+ *
+ * The contract.  Status, dest_len and consumed of stream i (_results) are exactly those a plain plan
+ * (zsc_hip_inflate_plan_create) reports with dest_caps[i] = dest_limits[i], for every input: a wrong
+ * Adler-32 or CRC-32 is Z_DATA_ERROR as a wrong ISIZE is, and a stream longer than its limit is
+ * Z_BUF_ERROR with dest_len equal to the limit.
+ *
+ * _run (d_dst is ignored and may be NULL: nothing is ever written through it), _results, _destroy,
+ * zsc_hip_inflate_plan_sections (the pieces a stream was checked in, in parallel, or 0),
+ * zsc_hip_inflate_plan_data_errors and zsc_hip_inflate_plan_scratch_bytes work on it;
+ * zsc_hip_inflate_plan_pack_enable and zsc_hip_inflate_plan_index_enable return Z_STREAM_ERROR.  As with
+ * chunks plans the parallel path only ever reports a clean Z_OK; a stream it cannot finish -- a check value
+ * that does not match, a broken chain, a limit passed, the work bound, any error -- is checked by the
+ * whole-stream decode from its start.  (A stream of 2 GiB or more of output is always left to that decode.)
+ * Scratch does not depend on dest_limits: 65 536 bytes per lane group of the launch -- four to a wavefront;
+ * wavefronts: a quarter of count, rounded up, and no more than fill the device -- a chunks plan's scratch
+ * for the streams longer than chunk_bytes (98 372 bytes per chunk; 8 per chunk after a stream's first,
+ * and at least 8), 4 bytes per stream for the check values, and 96 bytes per stream plus 16.  The
+ * environment variable
+ * ZSC_HIP_CHECK_GROUPS, read when the plan is created, caps the lane groups (rounded up to a whole
+ * wavefront): a test hook that makes every ring serve several streams.  A plan of any other kind
+ * allocates, launches and returns what it did without check plans. */
+ZlibReturn zsc_hip_inflate_plan_create_check(zsc_hip_inflate_plan **plan, U32 count,
+                                             const U32 *source_lens, const uint64_t *src_offsets,
+                                             const U32 *dest_limits, I32 window_bits, U32 chunk_bytes);
+/* The check value computed over the output of every stream of a check plan whose status is Z_OK -- CRC-32
+ * for a gzip stream, Adler-32 for a zlib or a raw one (the index blob's convention) -- and 0 for every
+ * other stream.  After _run; it waits for the run as _results does.  Z_STREAM_ERROR for a plan of any other
+ * kind and before the first run. */
+ZlibReturn zsc_hip_inflate_plan_check_values(zsc_hip_inflate_plan *plan, U32 *values);
+/* host-pointer batch through a check plan (default chunk_bytes).  dest_lens: in, the limits; out, the
+ * lengths.  source_lens: out, the bytes consumed.  statuses and check_values may be NULL. */
+ZlibReturn zsc_hip_uncompress_check_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                          U32 *dest_lens, I32 *statuses, U32 *check_values, I32 window_bits);
 
 /* seek-point indexes -------------------------------------------------------- */
 

@@ -114,6 +114,10 @@ def _load() -> C.CDLL:
     L.zsc_hip_inflate_plan_create_size.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p, C.c_int32,
                                                    C.c_uint32]
     L.zsc_hip_uncompress_sizes_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u32p, u32p, i32p, C.c_int32]
+    L.zsc_hip_inflate_plan_create_check.argtypes = L.zsc_hip_inflate_plan_create_size.argtypes
+    L.zsc_hip_inflate_plan_check_values.argtypes = [C.c_void_p, u32p]
+    L.zsc_hip_uncompress_check_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u32p, u32p, i32p, u32p,
+                                                 C.c_int32]
     L.zsc_hip_index_validate.argtypes = [C.c_char_p, C.c_uint64]
     L.zsc_hip_index_info.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(IndexHeader)]
     L.zsc_hip_index_range.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, u32p, u32p, u32p, u32p]
@@ -427,6 +431,23 @@ def uncompress_sizes_batch(sources: Sequence[bytes], limits: Sequence[int] | Non
     return rc, list(dlen) if rc == Z_OK else [], list(slen), list(stat)
 
 
+def uncompress_check_batch(sources: Sequence[bytes], limits: Sequence[int] | None = None,
+                           window_bits: int = DEF_WBITS) -> Tuple[int, List[int], List[int], List[int], List[int]]:
+    """zsc_hip_uncompress_check_batch: is every stream intact?  Found on the device without writing any
+    output (gzip -t for a batch).  limits as uncompress_sizes_batch.  Status, size and consumed are exactly
+    uncompress_batch's with dest_caps = limits: a wrong Adler-32 / CRC-32 is Z_DATA_ERROR.  check_values[i]
+    is the value computed over the output of a stream whose status is Z_OK (CRC-32 for gzip, Adler-32 for
+    zlib and raw streams) and 0 otherwise.  Returns (rc, sizes, consumed, statuses, check_values)."""
+    count = len(sources)
+    srcs = (C.c_char_p * count)(*sources)
+    slen = (C.c_uint32 * count)(*[len(s) for s in sources])
+    dlen = (C.c_uint32 * count)(*([NO_LIMIT] * count if limits is None else limits))
+    stat = (C.c_int32 * count)()
+    vals = (C.c_uint32 * count)()
+    rc = lib.zsc_hip_uncompress_check_batch(count, srcs, slen, dlen, stat, vals, window_bits)
+    return rc, list(dlen) if rc == Z_OK else [], list(slen), list(stat), list(vals)
+
+
 def uncompress_batch_auto(sources: Sequence[bytes], window_bits: int = DEF_WBITS, limit: int | None = None):
     """Inflate streams of unknown length: size them (uncompress_sizes_batch, every stream under `limit`
     if one is given), then run uncompress_chunks_batch with dest_caps[i] set to the reported size, so no
@@ -689,7 +710,10 @@ class InflatePlan(_Packing):
     align 16 or more, say, which then is the plan's input as it lies; src_bytes is not meaningful then.
     size_only=True makes a size plan (zsc_hip_inflate_plan_create_size): dest_caps are the limits (None: no
     limit), nothing is written, run() takes d_dst 0, and results() gives the sizes; a stream longer than
-    chunk_bytes is sized in parallel pieces (chunk_bytes 0 = the default, NO_LIMIT = never cut a stream)."""
+    chunk_bytes is sized in parallel pieces (chunk_bytes 0 = the default, NO_LIMIT = never cut a stream).
+    check_only=True makes a check plan (zsc_hip_inflate_plan_create_check) with the same arguments: the
+    streams are decoded into 64 KiB rings, so the check value of the trailer is compared as well -- results()
+    is a plain plan's at dest_caps = limits -- and check_values() hands out the values computed."""
     _pack_kind = "inflate"
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int] | None,
@@ -697,11 +721,15 @@ class InflatePlan(_Packing):
                  sections: bool = False, chunks: bool = False, chunk_bytes: int = 0, resync: bool = False,
                  keep_index: bool = False, indexes: Sequence[Optional[bytes]] | None = None,
                  ranges: Sequence[Optional[Tuple[int, int]]] | None = None,
-                 src_offsets: Sequence[int] | None = None, size_only: bool = False):
+                 src_offsets: Sequence[int] | None = None, size_only: bool = False,
+                 check_only: bool = False):
         self.count = n = len(source_lens)
+        if size_only and check_only:
+            raise ValueError("a plan is a size plan or a check plan, not both")
+        size_only = size_only or check_only  # (a check plan is laid out as a size plan)
         if size_only:
             if sections or chunks or resync or keep_index or indexes is not None or decode_order is not None:
-                raise ValueError("a size plan is no other kind of plan and takes no decode_order")
+                raise ValueError("a size or check plan is no other kind of plan and takes no decode_order")
             if dest_caps is None:
                 dest_caps = [NO_LIMIT] * n
         elif dest_caps is None:
@@ -731,9 +759,9 @@ class InflatePlan(_Packing):
         if sections and chunks:
             raise ValueError("a plan is a sections plan or a chunks plan, not both")
         if size_only:
-            rc = lib.zsc_hip_inflate_plan_create_size(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
-                                                      (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
-                                                      window_bits, chunk_bytes)
+            create = lib.zsc_hip_inflate_plan_create_check if check_only else lib.zsc_hip_inflate_plan_create_size
+            rc = create(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens), (C.c_uint64 * n)(*so),
+                        (C.c_uint32 * n)(*dest_caps), window_bits, chunk_bytes)
         elif indexes is not None:
             if len(indexes) != n or (ranges is not None and len(ranges) != n):
                 raise ValueError("one index (and one range) per stream")
@@ -817,6 +845,16 @@ class InflatePlan(_Packing):
         rc = lib.zsc_hip_inflate_plan_data_errors(self._h, out)
         if rc != Z_OK:
             raise RuntimeError(f"zsc_hip_inflate_plan_data_errors failed: {rc}")
+        return list(out)[:n]
+
+    def check_values(self) -> List[int]:
+        """After run() of a check plan: per stream whose status is Z_OK, the check value computed over its
+        output (CRC-32 for gzip, Adler-32 for zlib and raw streams); 0 for every other stream."""
+        n = self.count
+        out = (C.c_uint32 * max(n, 1))()
+        rc = lib.zsc_hip_inflate_plan_check_values(self._h, out)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_check_values failed: {rc}")
         return list(out)[:n]
 
     def scratch_bytes(self) -> int:

@@ -303,6 +303,13 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
  * INF_SEC_BITSTART | INF_SEC_COUNT is the piece variant of the same path: a piece's length, link, reach,
  * longest distance and end bit with no ring and no window. */
 #define INF_SEC_SIZE 128u
+/* the ring variant (inflate_check.h), with chk pointing to an InfCheck:
+ *   INF_SEC_RING     every output byte goes to a byte ring chk owns instead of dst (job.dst is never looked at),
+ *                    far match sources are read back from it, and the check value of the output is kept
+ *                    running in chk as the ring fills; the trailer is compared with that value.  Alone it is
+ *                    the whole stream as SEC = 0 decodes it (results to res / rs); with INF_SEC_BITSTART |
+ *                    INF_SEC_EXTWIN | INF_SEC_NOTRAIL it is the write pass of a chained piece. */
+#define INF_SEC_RING 256u
 #define INF_WIN 32768u   /* window entries: win[INF_WIN - d] is the byte d before the piece */
 #define INF_PH 0x8000u   /* a placeholder symbol of the 16-bit output */
 #define INF_PC_CANDS 4u  /* candidates per chunk */
@@ -355,14 +362,16 @@ typedef struct {
  * by a loop in here: wrapping the decoder in an outer loop doubles its register count (135
  * instead of 68 VGPRs, occupancy 3 instead of 7), and even the search alone, placed after the
  * decode loop, costs it a wave per SIMD; the sound streams would pay for the damaged ones. */
-template <uint32_t SEC = 0u>
+template <uint32_t SEC = 0u, class CK = void>
 DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume *rs, InfSecInfo *si = nullptr,
-                      InfPiece *pc = nullptr)
+                      InfPiece *pc = nullptr, CK *chk = nullptr)
 {
+    constexpr bool RING = (SEC & INF_SEC_RING) != 0u;
     constexpr bool PIECE_OUT = (SEC & (INF_SEC_SYM16 | INF_SEC_EXTWIN)) != 0u ||
                                (SEC & (INF_SEC_BITSTART | INF_SEC_COUNT)) == (INF_SEC_BITSTART | INF_SEC_COUNT);
     constexpr bool SIZE_ONLY = (SEC & INF_SEC_SIZE) != 0u;
-    constexpr bool SECTION = SEC != 0u && !SIZE_ONLY; /* results go to *si (and *pc) */
+    constexpr bool SECTION = (SEC & ~INF_SEC_RING) != 0u && !SIZE_ONLY; /* results go to *si (and *pc) */
+    (void)chk;
     const uint8_t *src = job.src;
     const uint32_t n = job.n, cap = job.cap;
     uint8_t *dst = job.dst;
@@ -428,6 +437,12 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     (void)pc_win;
     uint32_t sec_body = 0; /* (resync variants only) the header is behind: a data error is one in the blocks */
     (void)sec_body;
+    /* (the ring variant only) the ring and the end of the last quarter folded, kept here and not in *chk so
+     * that the symbol loop reads neither from memory */
+    uint8_t *rg = nullptr;
+    uint32_t rg_folded = 0;
+    (void)rg;
+    (void)rg_folded;
 
 /* top up the bit buffer to at least 32 bits (or to the end of the input) */
 #define INF_REFILL()                                                                          \
@@ -725,6 +740,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
 
     if constexpr ((SEC & INF_SEC_ERRSTATE) != 0u)
         sec_body = 1;
+    if constexpr (RING) {
+        chk->start((uint32_t)gzip);
+        rg = chk->ring;
+    }
 
     /* blocks */
     for (;;) {
@@ -766,6 +785,22 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                 }
                 WAVE_SYNC();
                 pos += can;
+            } else if constexpr (RING) {
+                for (uint32_t k = 0; k < can; k += 256u) {
+                    const uint32_t step = can - k < 256u ? can - k : 256u;
+                    FOR_GLANES
+                    {
+                        for (uint32_t j = (uint32_t)GLANE; j < step; j += GRP) {
+                            const uint8_t b = src[at + k + j];
+                            lds->stage[(pos + j) & (INF_STAGE - 1)] = b;
+                            chk->put(rg, rg_folded, pos + j, b);
+                        }
+                    }
+                    WAVE_SYNC();
+                    pos += step;
+                    if (CK::due(pos, rg_folded))
+                        rg_folded = chk->fold(pos, lds);
+                }
             } else
             for (uint32_t k = 0; k < can; k += 256u) {
                 const uint32_t step = can - k < 256u ? can - k : 256u;
@@ -888,6 +923,7 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                     pc_hdr |= pc_blocks == 0u;
             }
             /* symbols */
+        [[maybe_unused]] sym_again: /* (the ring variant comes back here from a fold) */
             WAVE_SYNC();
             LANEVAR(uint32_t, lfc);
             LANEVAR(uint32_t, lof);
@@ -938,6 +974,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
             for (;;) {
                 int sym;
                 for (;;) {
+                    if constexpr (RING) {
+                        if (CK::due(pos, rg_folded)) /* (a literal or a copy has completed a quarter of the ring: */
+                            INF_LEAVE(6);            /*  folded outside, like all that is rare, and back in) */
+                    }
                     INF_DECODE_R(&lds->lit, lfc, lof, lfc2, lof2, lmax, 4, sym);
                     if (sym >= 256) /* a length or the end of the block */
                         break;
@@ -945,6 +985,13 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                         INF_ON_FULL;
                     if constexpr ((SEC & INF_SEC_SYM16) != 0u) {
                         ON_GLANE0 { pc_ring[pos & (INF_WIN - 1u)] = (uint16_t)sym; }
+                        WAVE_SYNC();
+                    } else if constexpr (RING) {
+                        ON_GLANE0
+                        {
+                            lds->stage[pos & (INF_STAGE - 1)] = (uint8_t)sym;
+                            chk->put(rg, rg_folded, pos, (uint8_t)sym);
+                        }
                         WAVE_SYNC();
                     } else if constexpr ((SEC & INF_SEC_COUNT) == 0u) {
                         ON_GLANE0
@@ -1006,6 +1053,28 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                  * far more than the error of the reciprocal -- a handful of instructions where the
                  * integer division is ~30 */
                 const float rdist = RCP_F32((float)dist);
+                if constexpr (RING) {
+                    /* (as the copies below, with the ring for dst; a piece reads what lies before it from
+                     * its window) */
+                    for (uint32_t k = 0; k < can; k += GRP) {
+                        FOR_GLANES
+                        {
+                            uint32_t i = k + (uint32_t)GLANE;
+                            if (i < can) {
+                                const uint32_t q = (uint32_t)(((float)i + 0.5f) * rdist);
+                                const uint32_t s = pos - dist + (i - q * dist);
+                                uint8_t b;
+                                if ((SEC & INF_SEC_EXTWIN) != 0u && (int32_t)s < 0)
+                                    b = pc_win[INF_WIN + s];
+                                else
+                                    b = s + INF_STAGE >= pos + can ? lds->stage[s & (INF_STAGE - 1)] : chk->get(rg, s);
+                                lds->stage[(pos + i) & (INF_STAGE - 1)] = b;
+                                chk->put(rg, rg_folded, pos + i, b);
+                            }
+                        }
+                        WAVE_SYNC();
+                    }
+                } else
                 if constexpr ((SEC & INF_SEC_SYM16) != 0u) {
                     /* (a read never meets this copy's own writes: it lies before pos, and the slot of
                      * a write is read, if at all, by the same or a lower lane) */
@@ -1069,6 +1138,12 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
 #undef INF_LEAVE
             if (ev != 0) {
                 const uint32_t cls = ev >> 16;
+                if constexpr (RING) {
+                    if (cls == 6u) {
+                        rg_folded = chk->fold(pos, lds);
+                        goto sym_again;
+                    }
+                }
                 if (cls == 1u)
                     INF_ON_EXHAUST;
                 if (cls == 2u)
@@ -1104,6 +1179,8 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                     if (pc->cand[(uint64_t)m * INF_PC_CANDS + c] == b && hit == 0xffffffffu)
                         hit = c;
                 if (hit != 0xffffffffu) {
+                    if constexpr (RING)
+                        chk->fold_tail(pos, lds);
                     pc_link = m * INF_PC_CANDS + hit;
                     sec_sync = 1;
                     rc = INF_END;
@@ -1118,6 +1195,8 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
         uint32_t t;
         INF_TAKE(t, br.bits & 7u);
         (void)t;
+        if constexpr (RING)
+            chk->fold_tail(pos, lds); /* (the last, partial quarter) */
         if constexpr ((SEC & INF_SEC_NOTRAIL) != 0u) {
             rc = INF_END; /* (the trailer is checked by whoever put the sections together) */
             goto done;
@@ -1129,6 +1208,10 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
             if constexpr (SIZE_ONLY) {
                 if ((wrap & 4) && data_errors)
                     INF_BADX(32, 32); /* (the check value of an output with a hole in it) */
+            } else if constexpr (RING) {
+                const uint32_t got = gzip ? v : ((v >> 24) | ((v >> 8) & 0xff00u) | ((v & 0xff00u) << 8) | (v << 24));
+                if ((wrap & 4) && got != chk->value)
+                    INF_BADX(32, 32); /* :1333-1339 */
             } else
             if (wrap & 4) {
 #ifndef ZSC_WAVE_EMU

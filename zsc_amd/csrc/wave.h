@@ -131,7 +131,7 @@ static inline uint32_t emu_lds_cas(uint32_t *p, uint32_t expect, uint32_t v)
 #define CTZ32(x) __builtin_ctz(x)
 #define POPC64(x) __builtin_popcountll(x)
 #define CLZ64(x) __builtin_clzll(x)
-#define CLZ32(x) __builtin_clz(x)
+#define CLZ32(x) ((x) ? __builtin_clz(x) : 32) /* (callers pass 0: the longest distance of a piece may be 1) */
 static inline uint32_t emu_brev32(uint32_t v)
 {
     v = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);

@@ -31,6 +31,7 @@
 #include "inflate_resync.h"
 #include "inflate_index.h"
 #include "inflate_size.h"
+#include "inflate_check.h"
 #include "deflate_index.h"
 #include "deflate_verify.h"
 #include "pack.h"
@@ -1044,6 +1045,69 @@ __global__ __launch_bounds__(64) void k_size_finish(const uint8_t *__restrict__ 
     for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < P.nactive;
          a += gridDim.x * INF_PER_WAVE)
         size_finish(P, src, res, resume, a);
+}
+
+/* kernel 11 (inflate_check.h): the streams checked, nothing stored.  k_inflate_check is k_inflate's queue
+ * loop over the ring variant, each lane group with CHK_RING bytes of `rings`; ahead of it a check plan with
+ * chunks runs the chunks plan's launches with k_check_write in place of k_chk_write, and k_check_finish
+ * behind k_sec_finish */
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_inflate_check(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ rings, const ZdInfItem *__restrict__ items,
+    const uint32_t *__restrict__ order, InfResult *__restrict__ res, InfResume *__restrict__ resume,
+    uint32_t *__restrict__ values, uint32_t *__restrict__ pending, int32_t window_bits, uint32_t count)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    InfLds *lds = &lds_all[grp];
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds->cktab = crc_table;
+    InfCheck ck;
+    ck.ring = rings + (uint64_t)(blockIdx.x * INF_PER_WAVE + grp) * CHK_RING;
+    /* one queue, as k_inflate (pending[1]; longest input first); the next stream reuses the ring */
+    for (;;) {
+        uint32_t slot = 0;
+        if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+            slot = atomicAdd(pending + 1, 1u);
+        slot = (uint32_t)__shfl((int)slot, (int)(threadIdx.x & (64u - INF_GROUP)));
+        if (slot >= count)
+            break;
+        const uint32_t i = order[slot];
+        if (resume[i].state == 2u)
+            continue; /* finished by the chunked path */
+        const ZdInfItem it = items[i];
+        InfJob job;
+        job.src = src + it.src_off;
+        job.n = it.src_len;
+        job.dst = nullptr;
+        job.cap = it.dst_cap; /* the limit */
+        job.window_bits = window_bits;
+        if (check_stream(job, lds, &res[i], &resume[i], &ck, &values[i])) {
+            if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+                atomicAdd(pending, 1u); /* the host launches k_inflate_size for these */
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_check_write(
+    const uint8_t *__restrict__ src, IchkPlan P)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfSecInfo info[INF_PER_WAVE];
+    __shared__ InfPiece piece[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    chk_check_worker(P, src, &lds_all[grp], &info[grp], &piece[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_check_finish(IchkPlan P, const InfResume *__restrict__ resume,
+                                                     uint32_t *__restrict__ values)
+{
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < P.nactive;
+         a += gridDim.x * INF_PER_WAVE)
+        check_finish(P, resume, values, a);
 }
 
 /* the export of a chunks plan's index: the records of stream s's chain, each window's place in the
@@ -3500,6 +3564,11 @@ struct zsc_hip_inflate_plan {
     /* size plans only (inflate_size.h; with chunks they use cp and the chunks plan's record buffers, never
      * d_ring, d_win or d_chain_ck) */
     bool size_only = false, size_ran = false;
+    /* check plans only (inflate_check.h): size plans (size_only is set, and relaunches are the size decode)
+     * whose first launch decodes into rings; with chunks they use every buffer of a chunks plan */
+    bool check = false;
+    uint32_t check_waves = 0; /* wavefronts of k_inflate_check: d_rings holds CHK_RING bytes for each lane group */
+    DevBuf d_rings, d_ckval;
     bool indexed = false, idx_fixed = false;
     IidxPlan ip = {};
     uint32_t idx_active = 0;
@@ -3603,7 +3672,8 @@ static void inflate_plan_release(zsc_hip_inflate_plan *pl)
                       &pl->d_active, &pl->d_q, &pl->d_cstart, &pl->d_cstop, &pl->d_clink, &pl->d_clen,
                       &pl->d_chain_k, &pl->d_chain_off, &pl->d_chain_ck, &pl->d_cand, &pl->d_cused, &pl->d_creach,
                       &pl->d_want, &pl->d_ring, &pl->d_win, &pl->d_cerr, &pl->d_chain_fl, &pl->d_rst, &pl->d_sst0,
-                      &pl->d_q0, &pl->d_ipieces, &pl->d_iunits, &pl->d_ixs, &pl->d_idone, &pl->d_res0, &pl->d_resume0})
+                      &pl->d_q0, &pl->d_ipieces, &pl->d_iunits, &pl->d_ixs, &pl->d_idone, &pl->d_res0, &pl->d_resume0,
+                      &pl->d_rings, &pl->d_ckval})
         b->release();
 }
 
@@ -3786,9 +3856,11 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_chunks(zsc_hip_inflate_plan **
     return Z_OK;
 }
 
-extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **plan_out, U32 count,
-                                                       const U32 *source_lens, const uint64_t *src_offsets,
-                                                       const U32 *dest_limits, I32 window_bits, U32 chunk_bytes)
+/* a size plan, or (check) a check plan: the same items, queue order and chunk records, and for a check plan
+ * the chunks plan's rings, windows and slice check values, the lane groups' rings and the values */
+static ZlibReturn size_plan_create(zsc_hip_inflate_plan **plan_out, U32 count, const U32 *source_lens,
+                                   const uint64_t *src_offsets, const U32 *dest_limits, I32 window_bits,
+                                   U32 chunk_bytes, bool check)
 {
     ZSC_ASSERT(plan_out != Z_NULL);
     *plan_out = nullptr;
@@ -3808,6 +3880,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **pl
     DeviceScope scope;
     zsc_hip_inflate_plan *pl = *plan_out;
     pl->size_only = true;
+    pl->check = check;
     const uint32_t cb = chunk_bytes == 0 ? CHK_DEFAULT_BYTES : std::max<uint32_t>(chunk_bytes, CHK_MIN_BYTES);
     /* per stream longer than a chunk: its chunks; the scan visits every chunk but the first (any limit
      * will do: a piece is only counted, no position inside it is ever signed) */
@@ -3820,7 +3893,9 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **pl
         it.src_off = src_offsets[i];
         it.dst_off = 0;
         it.src_len = source_lens[i];
-        it.dst_cap = limits[i];
+        /* (a check plan's pieces sign positions in 32 bits, as a chunks plan's: a stream of 2 GiB or more is
+         * left to the whole-stream decode by this limit) */
+        it.dst_cap = check ? std::min<uint32_t>(limits[i], 0x7fffffffu) : limits[i];
         it.cap = 0;
         it.tile0 = (uint32_t)nchunks;
         it.ntiles = 0;
@@ -3847,6 +3922,18 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **pl
               pl->d_clen.ensure(4 * ch) && pl->d_chain_k.ensure(4 * ch) && pl->d_chain_off.ensure(4 * ch) &&
               pl->d_cand.ensure(8ull * INF_PC_CANDS * ch) && pl->d_cused.ensure(4 * ch) &&
               pl->d_creach.ensure(4 * ch) && pl->d_want.ensure(4 * ch);
+    if (check) {
+        /* ZSC_HIP_CHECK_GROUPS (a test hook): fewer lane groups, so that every ring is reused by several streams */
+        pl->check_waves = inflate_grid(count);
+        if (const char *e = getenv("ZSC_HIP_CHECK_GROUPS")) {
+            const long long g = atoll(e);
+            if (g > 0)
+                pl->check_waves = (uint32_t)std::min<long long>(pl->check_waves, (g + INF_PER_WAVE - 1) / INF_PER_WAVE);
+        }
+        ok = ok && pl->d_chain_ck.ensure(4 * ch) && pl->d_ring.ensure(2ull * INF_WIN * (nchunks ? ch : 0) + 16) &&
+             pl->d_win.ensure((uint64_t)INF_WIN * (nchunks ? ch : 0) + 16) &&
+             pl->d_rings.ensure((uint64_t)CHK_RING * pl->check_waves * INF_PER_WAVE) && pl->d_ckval.ensure(4 * nc);
+    }
     if (ok && count)
         ok = hipMemcpy(pl->d_sitems.p, items.data(), sizeof(IsecItem) * count, hipMemcpyHostToDevice) == hipSuccess;
     if (ok && !scan.empty())
@@ -3886,7 +3973,30 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **pl
     pl->ncand_total = nchunks;
     pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
                         (8ull * INF_PC_CANDS + 32) * ch;
+    if (check) {
+        P.sp.chain_ck = (uint32_t *)pl->d_chain_ck.p;
+        P.ring = (uint16_t *)pl->d_ring.p;
+        P.win = (uint8_t *)pl->d_win.p;
+        /* a chunks plan's scratch for the streams with chunks, a ring per lane group, a value per stream */
+        pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
+                            (8ull * INF_PC_CANDS + 36 + 3ull * INF_WIN) * nchunks +
+                            (uint64_t)CHK_RING * pl->check_waves * INF_PER_WAVE + 4 * nc;
+    }
     return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                       const U32 *source_lens, const uint64_t *src_offsets,
+                                                       const U32 *dest_limits, I32 window_bits, U32 chunk_bytes)
+{
+    return size_plan_create(plan_out, count, source_lens, src_offsets, dest_limits, window_bits, chunk_bytes, false);
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_check(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                        const U32 *source_lens, const uint64_t *src_offsets,
+                                                        const U32 *dest_limits, I32 window_bits, U32 chunk_bytes)
+{
+    return size_plan_create(plan_out, count, source_lens, src_offsets, dest_limits, window_bits, chunk_bytes, true);
 }
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_create_resync(zsc_hip_inflate_plan **plan_out, U32 count,
@@ -4098,6 +4208,36 @@ static void size_launch(zsc_hip_inflate_plan *pl, const void *d_src, hipStream_t
                        (InfResume *)pl->d_resume.p, (uint32_t *)pl->d_pending.p, pl->window_bits, pl->count);
 }
 
+/* the launches of a check plan: the chunks plan's (none when no stream is longer than a chunk) with the
+ * check-write pass for the write pass and the values copied out behind k_sec_finish, then k_inflate_check */
+static void check_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, hipStream_t st)
+{
+    const IchkPlan &P = pl->cp;
+    if (P.nactive != 0) {
+        const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
+        const uint32_t per_stream = std::max(1u, std::min(P.nactive, fill));
+        const uint32_t per_group = (per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE;
+        const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
+        const uint32_t scans = std::max(1u, std::min(P.sp.ntiles, fill * 4u));
+        hipLaunchKernelGGL(k_chk_setup, dim3(per_stream), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(k_chk_scan, dim3(scans), dim3(64), 0, st, (const uint8_t *)d_src, P);
+        hipLaunchKernelGGL(k_chk_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+        hipLaunchKernelGGL(k_chk_want, dim3(per_stream), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(k_chk_retry, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+        hipLaunchKernelGGL(k_chk_resolve, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P);
+        hipLaunchKernelGGL(k_chk_window, dim3(std::min<uint32_t>(P.nactive, (uint32_t)g_cus * 4u)), dim3(CHK_WINDOW_THREADS), 0, st, P);
+        hipLaunchKernelGGL(k_check_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
+        hipLaunchKernelGGL(k_sec_finish, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P.sp,
+                           (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+        hipLaunchKernelGGL(k_check_finish, dim3(per_group), dim3(64), 0, st, P, (const InfResume *)pl->d_resume.p,
+                           (uint32_t *)pl->d_ckval.p);
+    }
+    hipLaunchKernelGGL(k_inflate_check, dim3(pl->check_waves), dim3(64), 0, st, (const uint8_t *)d_src,
+                       (uint8_t *)pl->d_rings.p, (const ZdInfItem *)pl->d_items.p, (const uint32_t *)pl->d_order.p,
+                       (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p, (uint32_t *)pl->d_ckval.p,
+                       (uint32_t *)pl->d_pending.p, pl->window_bits, pl->count);
+}
+
 /* the launches of a resync plan, ahead of k_inflate: the sections plan's scan and setup, then its own */
 static void rsy_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
 {
@@ -4165,9 +4305,15 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         pl->size_ran = true;
         HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
         HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
+        if (pl->check)
+            HIP_TRY(hipMemsetAsync(pl->d_ckval.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
         (void)hipEventRecord(pl->ev0, st);
-        size_enqueue(pl, d_src, st);
-        size_launch(pl, d_src, st);
+        if (pl->check) {
+            check_enqueue(pl, d_src, st);
+        } else {
+            size_enqueue(pl, d_src, st);
+            size_launch(pl, d_src, st);
+        }
         (void)hipEventRecord(pl->ev1, st);
         pl->timed = true;
         HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
@@ -4541,6 +4687,82 @@ extern "C" ZlibReturn zsc_hip_uncompress_sizes_batch(U32 count, const U8 *const 
         source_lens[i] = used[i];
         if (statuses)
             statuses[i] = stat[i];
+    }
+    d_src.release();
+    zsc_hip_inflate_plan_destroy(pl);
+    return rc;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_check_values(zsc_hip_inflate_plan *pl, U32 *values)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(values != Z_NULL);
+    if (!pl->check || !pl->size_ran)
+        return Z_STREAM_ERROR;
+    if (pl->count == 0)
+        return Z_OK;
+    /* (the statuses are final once _results has relaunched what had to be) */
+    std::vector<I32> stat(pl->count);
+    ZlibReturn rc = zsc_hip_inflate_plan_results(pl, nullptr, nullptr, stat.data(), nullptr);
+    if (rc != Z_OK)
+        return rc;
+    HIP_TRY(hipMemcpy(values, pl->d_ckval.p, 4ull * pl->count, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    for (uint32_t i = 0; i < pl->count; i++)
+        if (stat[i] != Z_OK)
+            values[i] = 0;
+    return Z_OK;
+}
+
+/* host-pointer batch through a check plan (default chunk_bytes): the sources staged in one device buffer */
+extern "C" ZlibReturn zsc_hip_uncompress_check_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                                     U32 *dest_lens, I32 *statuses, U32 *check_values,
+                                                     I32 window_bits)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(sources != Z_NULL);
+    ZSC_ASSERT(source_lens != Z_NULL);
+    ZSC_ASSERT(dest_lens != Z_NULL);
+    if (count == 0)
+        return Z_OK;
+    if (zsc_hip_init(-1) != Z_OK)
+        return Z_STREAM_ERROR;
+    std::vector<uint64_t> so(count);
+    uint64_t sb = 0;
+    for (U32 i = 0; i < count; i++) {
+        so[i] = sb;
+        sb += ((uint64_t)source_lens[i] + 64u + 15u) & ~15ull;
+    }
+    zsc_hip_inflate_plan *pl = nullptr;
+    ZlibReturn rc = zsc_hip_inflate_plan_create_check(&pl, count, source_lens, so.data(), dest_lens, window_bits, 0);
+    if (rc != Z_OK)
+        return rc;
+    DevBuf d_src;
+    if (!d_src.ensure(sb + 64)) {
+        zsc_hip_inflate_plan_destroy(pl);
+        return Z_MEM_ERROR;
+    }
+    for (U32 i = 0; i < count && rc == Z_OK; i++) {
+        ZSC_ASSERT(sources[i] != Z_NULL);
+        if (source_lens[i] && hipMemcpy((uint8_t *)d_src.p + so[i], sources[i], source_lens[i],
+                                        hipMemcpyHostToDevice) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    std::vector<U32> outl(count), used(count), vals(count);
+    std::vector<I32> stat(count);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_run(pl, d_src.p, nullptr, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_results(pl, outl.data(), used.data(), stat.data(), nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_check_values(pl, vals.data());
+    for (U32 i = 0; i < count && rc == Z_OK; i++) {
+        dest_lens[i] = outl[i];
+        source_lens[i] = used[i];
+        if (statuses)
+            statuses[i] = stat[i];
+        if (check_values)
+            check_values[i] = vals[i];
     }
     d_src.release();
     zsc_hip_inflate_plan_destroy(pl);
