@@ -80,7 +80,16 @@
 #define SG_PICK_AHEAD 16u /* positions from p on whose chain lengths a search must find in the register cache */
 #endif
 #ifndef SG_EMPTY_SKIP
-#define SG_EMPTY_SKIP 0 /* (measured: text and incompressible data lose 3-5 % to the test, the table class gains 4 %) a pending match and an empty chain among the trigrams a longer one must contain: no search */
+#define SG_EMPTY_SKIP 0 /* a pending match and an empty chain among the trigrams a longer one must contain: no search.  How far ahead the next empty chain lies is worked out at the register cache's fill; a search with a chain compares it with prev_len.  (measured, DESIGN.md section 5h: the table class gains 7 %, text and incompressible data lose 0.2 and 1.8 %) */
+#endif
+#ifndef SG_LAZY_FILTER
+#define SG_LAZY_FILTER 1 /* the lane-parallel search (SG_EVAL_ONE) reads the candidates' bytes best - 3 .. best along with their first four, and a pass ends behind its first compare when no candidate can beat best; 0: the search as it was */
+#endif
+#ifndef SG_LAZY_PV_LATE
+#define SG_LAZY_PV_LATE 0 /* 1: the string at p is loaded behind the first compare, once a lane has something to compare on (measured slower: a second trip to the LDS) */
+#endif
+#ifndef SG_LAZY_COUNT
+#define SG_LAZY_COUNT(what, n) /* event counters of tests/emu_lazy */
 #endif
 #ifndef SG_FAR_OVER
 #define SG_FAR_OVER 128u /* the shortest chain in reach is longer than this: look at the far ones too */
@@ -520,29 +529,75 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
  * one instruction stream for all 64 of them, where the walk spends a long compare per candidate that
  * passes the pre-check); when one candidate is left after the first eight bytes the whole wave
  * compares the rest of it at once.  Sets best / where; `bail`: two candidates agree with p for more
- * than 4 GRP bytes, the walk below takes over. */
-#define SG_EVAL_ONE(E, B)                                                                        \
+ * than 4 GRP bytes, the walk below takes over.
+ *
+ * Searches that cannot win (SG_LAZY_FILTER).  The pass only ever changes best through a lane whose length,
+ * cut to cap, is above best; the first lane "to reach nice" is taken whatever its length, but is only
+ * used if that length is above best too.
+ *   - best >= cap: no length cut to cap is above best, the pass is skipped.  (The pass could have set
+ *     `bail` where the walk then finds the same nothing: cur_len <= prev_len either way.)
+ *   - 4 <= best < cap: a lane whose candidate differs from p somewhere in bytes best - 3 .. best has a common
+ *     prefix of at most best bytes.  It leaves _act with its _len at the lower bound 4 <= best and is never
+ *     chosen as the longest.  Nor was it ever the lane that reached nice: that takes nice <= its length <=
+ *     best, and nice = min(nice_match, lookahead) <= best means lookahead <= best (a pass is entered with
+ *     best < nice_match: prev_len < max_lazy <= nice_match for the first, tested for the others), which is
+ *     cap <= best, the case above.  The lanes that stay are compared from byte 4 on as before -- the four
+ *     bytes prove nothing about those in between -- and at every exit but `bail` each lane's length is exact,
+ *     so the choice among them is the same.  With fewer lanes the pass can get by where it gave up before
+ *     (never the other way round: the lanes still comparing are a subset); both ways give the walk's result.
+ *   - after the first compare, no lane to compare on and no lane longer than best (three bytes while best is
+ *     2; four, that is a lane in _act, while it is 3; more needs a lane in _act): the pass ends there, on
+ *     the ballot it has just made, before the compare steps, the long compare and the 64-lane minimum. */
+#define SG_EVAL_ONE(E, B)                                                                       \
     do {                                                                                      \
         LANEVAR(uint32_t, _q);                                                                \
         LANEVAR(uint32_t, _r);                                                                \
         LANEVAR(uint32_t, _len);                                                              \
         LANEVAR(int, _act);                                                                   \
+        LANEVAR(int, _has);                                                                   \
+        if (SG_LAZY_FILTER && best >= cap)                                                    \
+            break; /* (no candidate gets past cap: nothing to find) */                        \
         SG_COUNT(12, 1);                                                                      \
-        SG_PV_LOAD();                                                                         \
-        FOR_GLANES                                                                             \
+        if (!(SG_LAZY_FILTER && SG_LAZY_PV_LATE))                                             \
+            SG_PV_LOAD();                                                                     \
+        /* a match of four bytes or more pending: only a candidate that shares bytes 0 .. best with p can \
+         * be longer, so the four that end at best are read along with the first four (otherwise the \
+         * first four twice: no branch, and no second trip to the LDS) */                     \
+        const uint32_t _fo = SG_LAZY_FILTER && best >= 4u ? best - 3u : 0u;                   \
+        uint32_t _pb = s0123;                                                                 \
+        if (SG_LAZY_FILTER) {                                                                 \
+            SG_PEEKP(_fo, _pb);                                                               \
+            SG_LAZY_COUNT(0, best >= 4u);                                                     \
+        }                                                                                     \
+        FOR_GLANES                                                                            \
         {                                                                                     \
-            const uint32_t _v = (B)*GRP + (uint32_t)GLANE;                                     \
+            const uint32_t _v = (B)*GRP + (uint32_t)GLANE;                                    \
             const uint32_t q = tileA + (LV(E) & ZD_TILE_MASK) - (_v < nA ? 0u : ZD_TILE);     \
             const int live = _v < total && q > (_v == 0u ? hfloor : floor_pos);               \
             const uint32_t r = live ? lz_ridx<L>(st, q) : 0u;                                 \
             const uint32_t x = lds_u32(lds->ring, r) ^ s0123;                                 \
+            const uint32_t y = SG_LAZY_FILTER ? lds_u32(lds->ring, r + _fo) ^ _pb : 0u;       \
             const int m3 = live && (x & 0xffffffu) == 0u;                                     \
             LV(_q) = q;                                                                       \
             LV(_r) = r;                                                                       \
             LV(_len) = m3 ? (x == 0u ? 4u : 3u) : 0u;                                         \
-            LV(_act) = m3 && x == 0u;                                                         \
+            LV(_act) = m3 && (x | y) == 0u;                                                   \
+            LV(_has) = m3;                                                                    \
         }                                                                                     \
-        uint64_t _am = GBALLOT(_act);                                                          \
+        uint64_t _am = GBALLOT(_act);                                                         \
+        if (SG_LAZY_FILTER) {                                                                 \
+            /* nobody to compare on and nobody longer than best (three bytes while best is 2; four, \
+             * that is a lane to compare on, while it is 3; more needs such a lane): the pass is over */ \
+            const uint64_t _hm = best >= 3u ? _am : GBALLOT(_has);                            \
+            if (_hm == 0) {                                                                   \
+                SG_LAZY_COUNT(1, 1);                                                          \
+                break;                                                                        \
+            }                                                                                 \
+            if (SG_LAZY_PV_LATE && _am != 0)                                                  \
+                SG_PV_LOAD();                                                                 \
+        }                                                                                     \
+        if (_am != 0 && 4u < cap)                                                             \
+            SG_LAZY_COUNT(3, 1);                                                              \
         uint32_t _k = 1;                                                                      \
         while (_am != 0 && 4u * _k < cap) {                                                   \
             if (_k >= GRP) {                                                                  \
@@ -562,6 +617,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
                 break;                                                                        \
             }                                                                                 \
             const uint32_t _pk = GREADLANE(pv, _k);                                            \
+            SG_LAZY_COUNT(2, 1);                                                              \
             FOR_GLANES                                                                         \
             {                                                                                 \
                 if (LV(_act)) {                                                               \
@@ -1004,6 +1060,18 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 LV(mcp) = look_x < 258u ? look_x : 258u;
                 LV(mni) = job.cfg.nice < look_x ? job.cfg.nice : look_x;
             }
+            if (SG_EMPTY_SKIP) {
+                /* how far ahead of each position the next one with an EMPTY chain lies (one that owns a string:
+                 * x + 3 <= n is what `ok` above says), plus 2, below the match limit in mcp; 0xffff: none in the cache */
+                LANEVAR(int, empty);
+                FOR_GLANES { LV(empty) = LV(mto) == 0u && (uint64_t)p + (uint32_t)GLANE + 3u <= job.n; }
+                const uint64_t em = GBALLOT(empty) >> 1;
+                FOR_GLANES
+                {
+                    const uint64_t ahead = em >> (uint32_t)GLANE;
+                    LV(mcp) = (LV(mcp) << 16) | (ahead ? (uint32_t)CTZ64(ahead) + 3u : 0xffffu);
+                }
+            }
         }
         const uint32_t s0123 = GREADLANE(mby, p - mt_at);
         const uint32_t prev_len = cur_len, prev_at = cur_at;
@@ -1032,15 +1100,12 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
              * them has been seen before -- if one of them (of those whose chain lengths are in the
              * register cache) has an EMPTY chain, there is nothing longer and no need to look. */
             int none_longer = 0;
-            if (SG_EMPTY_SKIP && total != 0 && prev_len >= 3u) {
-                LANEVAR(int, empty);
-                const uint32_t l0 = p - mt_at;
-                FOR_GLANES
-                {
-                    const uint32_t l = (uint32_t)GLANE;
-                    LV(empty) = l > l0 && l <= l0 + (prev_len - 2u) && LV(mto) == 0u && (uint64_t)mt_at + l + 3u <= job.n;
-                }
-                none_longer = GBALLOT(empty) != 0;
+            uint32_t capd = 0;
+            if (SG_EMPTY_SKIP && total != 0) {
+                /* (how far ahead the next empty chain lies, plus 2, comes with the match limit from the cache's
+                 * fill; it is at least 3, so the test fails by itself while no match is pending) */
+                capd = GREADLANE(mcp, p - mt_at);
+                none_longer = (capd & 0xffffu) <= prev_len;
                 SG_COUNT(9, (unsigned)none_longer);
             }
             if (total != 0 && !none_longer) {
@@ -1048,7 +1113,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 const int32_t hiA = (int32_t)GREADLANE(mha, p - mt_at), hiB = (int32_t)GREADLANE(mhb, p - mt_at);
                 const uint32_t tileA = p & ~ZD_TILE_MASK;
                 uint32_t floor_pos = GREADLANE(mfl, p - mt_at);
-                const uint32_t cap = GREADLANE(mcp, p - mt_at), nice = GREADLANE(mni, p - mt_at);
+                const uint32_t cap = SG_EMPTY_SKIP ? capd >> 16 : GREADLANE(mcp, p - mt_at), nice = GREADLANE(mni, p - mt_at);
                 uint32_t best = prev_len, where = cur_at, sb = 0;
                 uint32_t budget = prev_len >= job.cfg.good ? job.cfg.chain >> 2 : job.cfg.chain;
                 int fin = 0, head_seen = 0;
