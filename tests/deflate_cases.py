@@ -109,8 +109,10 @@ def body_offset(stream, window_bits):
     return 2
 
 
-def walk(stream, window_bits=15):
-    """-> (blocks, output bytes, bit position after the last block)"""
+def walk(stream, window_bits=15, tokens=None):
+    """-> (blocks, output bytes, bit position after the last block).  A list given as `tokens` receives the
+    parse the stream states: (input position, length, distance) per copy, (position, 1, 0) per literal and
+    (position, length, -1) for the bytes of a stored block, which says nothing about its parse."""
     r = _Bits(stream, 8 * body_offset(stream, window_bits))
     out = bytearray()
     blocks = []
@@ -133,6 +135,8 @@ def walk(stream, window_bits=15):
             at = r.pos >> 3
             if at + n > len(stream):
                 raise ValueError("stored block runs past the end")
+            if tokens is not None and n:
+                tokens.append((len(out), n, -1))
             out += stream[at:at + n]
             r.pos += 8 * n
             b.stored_len = n
@@ -174,6 +178,8 @@ def walk(stream, window_bits=15):
                 s = _decode(r, lt, lw)
                 b.lit_hist[s] += 1
                 if s < 256:
+                    if tokens is not None:
+                        tokens.append((len(out), 1, 0))
                     out.append(s)
                 elif s == 256:
                     b.sym_pos.append(p)
@@ -192,6 +198,8 @@ def walk(stream, window_bits=15):
                     dist = DIST_BASE[d] + r.take(DIST_EXTRA[d])
                     if dist > len(out):
                         raise ValueError("distance too far back")
+                    if tokens is not None:
+                        tokens.append((len(out), n, dist))
                     if dist >= n:
                         out += out[-dist:len(out) - dist + n]
                     else:

@@ -14,6 +14,11 @@
 
 struct uint4 { uint32_t x, y, z, w; };
 
+/* path hooks of the parsers (SG_PATH in zsc_amd/csrc/lz_parse*.h): how often each data-dependent branch ran;
+ * the ids are listed in tests/parser_cases.py */
+extern "C" { unsigned long long g_sg_path[128]; }
+#define SG_PATH(id) (g_sg_path[(id)]++)
+#define SG_PATH_IF(cond, id) do { if (cond) g_sg_path[(id)]++; } while (0)
 #include "../../zsc_amd/csrc/hash_sort.h"
 #include "../../zsc_amd/csrc/lz_parse.h"
 /* event counters for tools/seg_stats.py: [0] batches, [1] long compares; per segment a

@@ -29,6 +29,13 @@
 #include "wave.h"
 #include "zsc_dev.h"
 
+/* Path hooks of the host emulation (tests/emu): which data-dependent branch of a search or of the parse ran.
+ * Empty in the product.  The ids and what they mean are listed in tests/parser_cases.py (PATHS). */
+#ifndef SG_PATH
+#define SG_PATH(id)
+#define SG_PATH_IF(cond, id) /* (the condition is the hook's alone: the product does not evaluate it) */
+#endif
+
 #define LZ_PR 512u /* positions covered by the rank/hib look-ahead ring */
 #define LZ_MIRROR 512u /* bytes of the window ring's start kept a second time behind its end */
 #define LZ_PR_FAST 128u /* the same in the greedy parser's LDS */
@@ -502,6 +509,10 @@ DEV void lz_mark_holes(L *lds, const LzState &st, uint32_t old_n, uint32_t p_nex
 #define LZ_MEMB_ALL(q) 1
 #define LZ_MEMB_LAZY(q) (!lz_is_hole<L>(lds, st, (q)))
 #define LZ_MEMB_INS(q) ((lds->ins[lz_ridx<L>(st, (q)) >> 5] >> (lz_ridx<L>(st, (q)) & 31u)) & 1u)
+/* (for the path hooks: is MEMB the greedy parser's test?) */
+#define LZ_MEMB_ALL_GREEDY 0
+#define LZ_MEMB_LAZY_GREEDY 0
+#define LZ_MEMB_INS_GREEDY 1
 
 /* Evaluate one batch of 64 sorted entries (ENT, newest first) that lie in the tile
  * starting at TPOS.  Sets `verdict`: 0 continue with the next batch of this run,
@@ -547,6 +558,7 @@ DEV void lz_mark_holes(L *lds, const LzState &st, uint32_t old_n, uint32_t p_nex
             if (BALLOT(_edge) != 0) {                                                         \
                 int _blk;                                                                     \
                 LZ_HEAD_BLOCKED(sc.p - job.cfg.max_dist, sc.p, MEMB, _blk);                   \
+                SG_PATH(_blk ? 66 : 67);                                                      \
                 FOR_LANES                                                                     \
                 {                                                                             \
                     if (LV(_edge))                                                            \
@@ -555,8 +567,14 @@ DEV void lz_mark_holes(L *lds, const LzState &st, uint32_t old_n, uint32_t p_nex
             }                                                                                 \
         }                                                                                     \
         const uint64_t _m_alive = BALLOT(_alive);                                             \
+        SG_PATH_IF(MEMB##_GREEDY && (_m_reach & ~_m_in), 68); /* in reach, never inserted by the greedy parser */\
+        FOR_LANES                                                                             \
+        {                                                                                     \
+            SG_PATH_IF(LV(_inb) && sc.p - LV(_q) == job.cfg.max_dist, LV(_alive) ? 64 : 65);  \
+        }                                                                                     \
         if (!sc.head_seen) {                                                                  \
             if (_m_in == 0) {                                                                 \
+                SG_PATH_IF(_m_hash & ~_m_reach, 69);                                          \
                 if (_m_hash & ~_m_reach)                                                      \
                     (verdict) = 3; /* whatever heads the chain is NIL or too far */           \
                 else /* bucket entries, but none of them is in the chain: keep looking */     \
@@ -564,6 +582,7 @@ DEV void lz_mark_holes(L *lds, const LzState &st, uint32_t old_n, uint32_t p_nex
                 break;                                                                        \
             }                                                                                 \
             if (!((_m_alive >> _head_lane) & 1ull)) {                                         \
+                SG_PATH(69);                                                                  \
                 (verdict) = 3; /* chain head is NIL or too far: longest_match not called */   \
                 break;                                                                        \
             }                                                                                 \
@@ -594,6 +613,7 @@ DEV void lz_mark_holes(L *lds, const LzState &st, uint32_t old_n, uint32_t p_nex
                 sc.where = _qj;                                                               \
                 sc.best = _len;                                                               \
                 if (_len >= sc.nice || --sc.budget == 0) {                                    \
+                    SG_PATH(_len >= sc.nice ? 70 : 71);                                       \
                     (verdict) = 2;                                                            \
                     break;                                                                    \
                 }                                                                             \
@@ -610,6 +630,7 @@ DEV void lz_mark_holes(L *lds, const LzState &st, uint32_t old_n, uint32_t p_nex
                 _todo = BALLOT(_pass);                                                        \
             } else {                                                                          \
                 if (--sc.budget == 0) {                                                       \
+                    SG_PATH(71);                                                              \
                     (verdict) = 2;                                                            \
                     break;                                                                    \
                 }                                                                             \
@@ -617,6 +638,7 @@ DEV void lz_mark_holes(L *lds, const LzState &st, uint32_t old_n, uint32_t p_nex
             }                                                                                 \
         }                                                                                     \
         if ((verdict) == 0) {                                                                 \
+            SG_PATH_IF(_ends, 72);                                                            \
             if (_ends)                                                                        \
                 (verdict) = 2;                                                                \
             else if (_m_hash != ~0ull)                                                        \
@@ -712,6 +734,7 @@ DEV void lz_parse_lazy(const LzJob &job, L *lds)
         const uint32_t prev_len = cur_len, prev_at = cur_at;
         const int searching = look >= 3 && prev_len < job.cfg.lazy;
         cur_len = 2;
+        SG_PATH_IF(look >= 3 && !searching, 73);
 
         if (searching) {
             /* this position's first batches: prefetched one search ago, or fetched now */
@@ -747,6 +770,7 @@ DEV void lz_parse_lazy(const LzJob &job, L *lds)
             sc.nice = job.cfg.nice < look ? job.cfg.nice : look;
             sc.best = prev_len;
             sc.budget = prev_len >= job.cfg.good ? job.cfg.chain >> 2 : job.cfg.chain;
+            SG_PATH_IF(prev_len >= job.cfg.good, 74);
             sc.where = cur_at;
             sc.head_seen = 0;
 
@@ -770,8 +794,10 @@ DEV void lz_parse_lazy(const LzJob &job, L *lds)
                 cur_at = sc.where;
                 cur_len = sc.best < look ? sc.best : look;
                 if (cur_len <= 5 &&
-                    (job.strategy == 1 || (cur_len == 3 && p - cur_at > ZD_TOO_FAR)))
+                    (job.strategy == 1 || (cur_len == 3 && p - cur_at > ZD_TOO_FAR))) {
+                    SG_PATH(job.strategy == 1 ? 76 : 75);
                     cur_len = 2;
+                }
             }
         }
         if (prev_len >= 3 && cur_len <= prev_len) {
@@ -969,6 +995,7 @@ DEV void lz_parse_greedy(const LzJob &job, L *lds)
                 }
                 p++;
             } else {
+                SG_PATH(77);
                 p += len;
                 len = 0;
             }

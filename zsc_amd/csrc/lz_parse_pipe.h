@@ -152,6 +152,7 @@ DEV void sg_pipe_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr)
         const uint32_t xp = UNI(lds->wv[ks].exit_p);
         sg_append(job, &lds->out, scr.tok + ks * SG_TOKCAP, ft, UNI(lds->wv[ks].ntok), 1, 1u, ZD_MIN_LOOKAHEAD);
         if (kind == SG_EXIT_SYNCED) {
+            SG_PATH(56);
             k = xp / SG_G; /* (beyond k: a parser only hands over past its own segment) */
             cxp = xp;
             ft = 0;
@@ -162,6 +163,7 @@ DEV void sg_pipe_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr)
              * parsed again from this exact state, once its own speculative parse is out of the way */
             const uint32_t xl = UNI(lds->wv[ks].exit_len), xa = UNI(lds->wv[ks].exit_at);
             const uint32_t xn = UNI(lds->wv[ks].exit_pending);
+            SG_PATH(kind == SG_EXIT_UNSYNCED ? 57 : 58);
             k = xp / SG_G;
             ft = 0;
             ON_LANE0
@@ -180,6 +182,7 @@ DEV void sg_pipe_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr)
             return;
         }
         /* SG_EXIT_END: the parse reached the end of the input */
+        SG_PATH(59);
         sg_end_of_input(job, lds, UNI(lds->wv[ks].exit_pending), xp);
         ON_LANE0 { LDS_STORE_REL(&lds->finished, 1u); }
         WAVE_SYNC();

@@ -421,6 +421,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
             if (GBALLOT(_edge) != 0) {                                                         \
                 int _blk;                                                                     \
                 SG_HEAD_BLOCKED(p - job.cfg.max_dist, p, LZ_MEMB_ALL, _blk);                  \
+                SG_PATH(_blk ? 18 : 19);                                                      \
                 if (!_blk) {                                                                  \
                     FOR_GLANES                                                                 \
                     {                                                                         \
@@ -433,6 +434,10 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
             }                                                                                 \
         }                                                                                     \
         const uint64_t _m_dead = GBALLOT(_dead);                                               \
+        FOR_GLANES                                                                             \
+        {                                                                                     \
+            SG_PATH_IF(LV(_dead) && p - LV(_q) == job.cfg.max_dist, 15);                      \
+        }                                                                                     \
         SG_COUNT(0, 1);                                                                       \
         FOR_GLANES                                                                             \
         {                                                                                     \
@@ -457,6 +462,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
             const uint64_t _below = _j < 64 ? (_todo & ((1ull << _j) - 1ull)) : _todo;        \
             const uint32_t _nb = (uint32_t)POPC64(_below);                                    \
             if (_nb >= budget) {                                                              \
+                SG_PATH(22);                                                                  \
                 fin = 1; /* the chain budget ends on a candidate that changes nothing */      \
                 break;                                                                        \
             }                                                                                 \
@@ -473,11 +479,13 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
                 best = _len;                                                                  \
                 _improved = 1;                                                                \
                 if (_len >= nice) {                                                           \
+                    SG_PATH(24);                                                              \
                     fin = 1;                                                                  \
                     break;                                                                    \
                 }                                                                             \
             }                                                                                 \
             if (--budget == 0) {                                                              \
+                SG_PATH(23);                                                                  \
                 fin = 1;                                                                      \
                 break;                                                                        \
             }                                                                                 \
@@ -496,6 +504,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
                 _todo &= ~((2ull << _j) - 1ull);                                              \
             }                                                                                 \
         }                                                                                     \
+        SG_PATH_IF(_m_dead != 0 && !fin, 25);                                                 \
         if (_m_dead != 0 && !fin)                                                             \
             fin = 1; /* the chain leaves the window (:1519) */                                \
     } while (0)
@@ -555,9 +564,11 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
         LANEVAR(uint32_t, _len);                                                              \
         LANEVAR(int, _act);                                                                   \
         LANEVAR(int, _has);                                                                   \
+        SG_PATH_IF(SG_LAZY_FILTER && best >= cap, 9);                                         \
         if (SG_LAZY_FILTER && best >= cap)                                                    \
             break; /* (no candidate gets past cap: nothing to find) */                        \
         SG_COUNT(12, 1);                                                                      \
+        SG_PATH(0 + (B));                                                                     \
         if (!(SG_LAZY_FILTER && SG_LAZY_PV_LATE))                                             \
             SG_PV_LOAD();                                                                     \
         /* a match of four bytes or more pending: only a candidate that shares bytes 0 .. best with p can \
@@ -574,6 +585,8 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
             const uint32_t _v = (B)*GRP + (uint32_t)GLANE;                                    \
             const uint32_t q = tileA + (LV(E) & ZD_TILE_MASK) - (_v < nA ? 0u : ZD_TILE);     \
             const int live = _v < total && q > (_v == 0u ? hfloor : floor_pos);               \
+            SG_PATH_IF(_v < total && p - q == job.cfg.max_dist, live ? 10 : 11);              \
+            SG_PATH_IF(_v == 0u && !live, 12);                                                \
             const uint32_t r = live ? lz_ridx<L>(st, q) : 0u;                                 \
             const uint32_t x = lds_u32(lds->ring, r) ^ s0123;                                 \
             const uint32_t y = SG_LAZY_FILTER ? lds_u32(lds->ring, r + _fo) ^ _pb : 0u;       \
@@ -590,6 +603,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
              * that is a lane to compare on, while it is 3; more needs such a lane): the pass is over */ \
             const uint64_t _hm = best >= 3u ? _am : GBALLOT(_has);                            \
             if (_hm == 0) {                                                                   \
+                SG_PATH(13);                                                                  \
                 SG_LAZY_COUNT(1, 1);                                                          \
                 break;                                                                        \
             }                                                                                 \
@@ -601,6 +615,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
         uint32_t _k = 1;                                                                      \
         while (_am != 0 && 4u * _k < cap) {                                                   \
             if (_k >= GRP) {                                                                  \
+                SG_PATH(8);                                                                   \
                 bail = 1;                                                                     \
                 break;                                                                        \
             }                                                                                 \
@@ -641,6 +656,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
             const uint64_t _mn = GBALLOT(_nice);                                               \
             const uint32_t _kk = _mn ? GREADLANE(_key, CTZ64(_mn)) : GMIN_U32(_key);           \
             const uint32_t _l = 511u - (_kk >> 8);                                            \
+            SG_PATH_IF(_mn != 0 && _l > best, 4 + (B));                                       \
             if (_l > best) {                                                                  \
                 best = _l;                                                                    \
                 where = GREADLANE(_q, _kk & 0xffu);                                            \
@@ -673,6 +689,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
         if (job.cfg.hbits != 15u && floor_pos > st.base && p - floor_pos == job.cfg.max_dist) { \
             int _blk; /* the position at exactly MAX_DIST counts if it heads the reference's chain */ \
             SG_HEAD_BLOCKED(floor_pos, p, LZ_MEMB_ALL, _blk);                                 \
+            SG_PATH(_blk ? 20 : 21);                                                          \
             if (!_blk)                                                                        \
                 _qlo = floor_pos;                                                             \
         }                                                                                     \
@@ -735,6 +752,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
                         best = _len;                                                          \
                         _moved = 1;                                                           \
                         if (_len >= nice) {                                                   \
+                            SG_PATH(36);                                                      \
                             fin = 1;                                                          \
                             break;                                                            \
                         }                                                                     \
@@ -757,6 +775,7 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
             }                                                                                 \
             if (fin || _moved)                                                                \
                 continue;                                                                     \
+            SG_PATH_IF(_R0 <= _rlo, 35);                                                      \
             if (_R0 <= _rlo)                                                                  \
                 break; /* the sweep reached the far end of the window */                      \
             _qn = _R0 - 1u - _off;                                                            \
@@ -961,6 +980,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 mt_at = p + 4096u; /* (the window has moved: the register cache holds values that depend on it) */
             look = st.data_end - p;
             if (look == 0) {
+                SG_PATH(45);
                 exit_kind = SG_EXIT_END;
                 break;
             }
@@ -972,6 +992,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
             if (PIPE)
                 E = sg_pipe_limit(lds, job.n);
             if (p >= E) {
+                SG_PATH(44);
                 exit_kind = SG_EXIT_LAST;
                 break;
             }
@@ -983,11 +1004,13 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 const uint32_t tword = GUNI(LDS_LOAD_ACQ(&lds->trace[ts][r >> 5]));
                 if (((tword >> (r & 31u)) & 1u) &&
                     ((GUNI(lds->tkind[ts][r >> 5]) >> (r & 31u)) & 1u) == (uint32_t)pending) {
+                    SG_PATH(pending ? 42 : 41);
                     exit_kind = SG_EXIT_SYNCED;
                     break;
                 }
             }
             if (p >= e_s + SG_OV) {
+                SG_PATH(43);
                 exit_kind = SG_EXIT_UNSYNCED;
                 break;
             }
@@ -1093,6 +1116,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
         /* (look >= 3 need not be asked: within MIN_LOOKAHEAD of the end of the window's data fill_window has run,
          * so fewer than three bytes are only left at the end of the input, where positions own no string and
          * their chains are empty: total == 0 below) */
+        SG_PATH_IF(look >= 3 && prev_len >= job.cfg.lazy, 39);
         if (prev_len < job.cfg.lazy && !known) {
             const uint32_t rp = lz_ridx<L>(st, p);
             const uint32_t nA = GREADLANE(mna, p - mt_at), total = GREADLANE(mto, p - mt_at);
@@ -1116,6 +1140,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 const uint32_t cap = SG_EMPTY_SKIP ? capd >> 16 : GREADLANE(mcp, p - mt_at), nice = GREADLANE(mni, p - mt_at);
                 uint32_t best = prev_len, where = cur_at, sb = 0;
                 uint32_t budget = prev_len >= job.cfg.good ? job.cfg.chain >> 2 : job.cfg.chain;
+                SG_PATH_IF(prev_len >= job.cfg.good, 40);
                 int fin = 0, head_seen = 0;
                 LANEVAR(uint32_t, e0);
                 LANEVAR(uint32_t, e1);
@@ -1177,11 +1202,14 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 if (head_ok && p - q0 == job.cfg.max_dist && job.cfg.hbits != 15u) {
                     int blocked;
                     SG_HEAD_BLOCKED(q0, p, LZ_MEMB_ALL, blocked);
+                    SG_PATH(blocked ? 16 : 17);
                     head_ok = !blocked;
                 }
                 if (!head_ok) {
+                    SG_PATH(26);
                     fin = 2; /* no chain head in the window: longest_match is not called */
                 } else {
+                    SG_PATH_IF(p - q0 == job.cfg.max_dist, 14);
                     head_seen = 1;
                     if (best >= look)
                         fin = 1;
@@ -1229,6 +1257,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                              * thousands of entries): the two chains that end at the byte which has to match
                              * next are worth a trip to memory. */
                             if (tmin > SG_FAR_OVER && l1 >= GRP) {
+                                SG_PATH(28);
                                 for (uint32_t o = best - 3u; o <= best - 2u; o++) {
                                     if (p + o - mt_at >= GRP && (uint64_t)p + o + 3u <= job.n) {
                                         uint32_t c, rhx;
@@ -1242,6 +1271,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                                         }
                                         const uint32_t t = (c & 0xffffu) + (c >> 16);
                                         if (t < tmin) {
+                                            SG_PATH(29);
                                             tmin = t;
                                             j = o;
                                             nAj = c & 0xffffu;
@@ -1367,6 +1397,8 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                                     best = len;
                                     bnd = qx;
                                     nrec++;
+                                    SG_PATH_IF(nrec == 3u, 27);
+                                    SG_PATH_IF(j != 0u, 38);
                                     if (qs == 0xffffffffu && best >= 5u)
                                         qs = where;
                                     if (best >= nice)
@@ -1388,15 +1420,19 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                             const uint32_t rk = (uint32_t)hiA + 1u, hb = (uint32_t)hiB;
                             const uint32_t r1 = GUNI((uint32_t)job.rank[where]);
                             const uint32_t newer = (where >> 15) == (p >> 15) ? rk - 1u - r1 : nA + (hb - r1);
+                            SG_PATH((where >> 15) == (p >> 15) ? 32 : 33);
                             if (qs == p) {
+                                SG_PATH(30);
                                 between = newer;
                             } else {
+                                SG_PATH(31);
                                 const uint32_t r0 = GUNI((uint32_t)job.rank[qs]);
                                 between = newer - ((qs >> 15) == (p >> 15) ? rk - 1u - r0 : nA + (hb - r0)) - 1u;
                             }
                         }
                         if (nrec + between >= budget0) {
                             SG_COUNT(8, 1);
+                            SG_PATH(47);
                             /* the reference's walk, as far as the last step's candidate: nothing beyond it
                              * is longer, so nothing beyond it changes the result */
                             if (where - 1u > floor_pos)
@@ -1422,6 +1458,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 }
                 if (fin) {
                 } else if (sweep) {
+                    SG_PATH(34);
                     SG_SWEEP(q0);
                 } else {
                     if (stair && total > GRP) {
@@ -1461,11 +1498,14 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                     cur_at = where;
                     cur_len = best < look ? best : look;
                     if (cur_len <= 5) { /* :2038-2047 */
-                        if (job.strategy == 1)
+                        if (job.strategy == 1) {
+                            SG_PATH(49);
                             cur_len = 2;
-                        else if (cur_len == 3) {
-                            if (p - cur_at > ZD_TOO_FAR)
+                        } else if (cur_len == 3) {
+                            if (p - cur_at > ZD_TOO_FAR) {
+                                SG_PATH(48);
                                 cur_len = 2;
+                            }
                         }
                     }
                 }

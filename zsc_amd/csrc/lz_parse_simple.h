@@ -130,6 +130,7 @@ DEV void lz_parse_rle(const LzJob &job, SpLds *lds)
             sg_append(job, &lds->out, lds->tok, 0, cnt, 1, 0u, ZD_MAX_MATCH + 1u);
             p = f;
         }
+        SG_PATH_IF(am == 0, 80);
         if (am == 0 || p >= n)
             continue;
         /* the run at p: bytes equal to in[p-1], at most 258 and at most what is left (:2156-2169) */
@@ -149,6 +150,7 @@ DEV void lz_parse_rle(const LzJob &job, SpLds *lds)
                 break;
             }
         }
+        SG_PATH(len == ZD_MAX_MATCH ? 82 : len == n - p ? 83 : 81);
         ON_LANE0 { lds->tok[0] = (1u << 16) | (len - 3u); }
         WAVE_SYNC();
         sg_append(job, &lds->out, lds->tok, 0, 1, 1, 0u, ZD_MAX_MATCH + 1u);
