@@ -1,7 +1,7 @@
 /*
  * emu_check.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program that checks streams with the check
  * path (zsc_amd/csrc/inflate_check.h) on the lane emulation (wave.h, -DZSC_WAVE_EMU), kernel by kernel
- * as the runtime enqueues them (zsc_hip_runtime.hip, check_enqueue): setup -> scan -> count -> want ->
+ * as the runtime enqueues them (zsc_hip_runtime.hip, chk_enqueue): setup -> scan -> count -> want ->
  * retry -> resolve -> window -> check-write -> finish for a stream longer than a chunk, then the
  * whole-stream ring decode for a stream that did not finish, with relaunches through the size decode.
  *
@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../zsc_amd/csrc/inflate_check.h"
+#include "../../zsc_amd/csrc/inflate_plan_layout.h"
 
 static InfLds *new_lds()
 {
@@ -44,16 +45,12 @@ static int check_one(const uint8_t *src, uint32_t n, int window_bits, uint32_t l
     std::vector<uint8_t> in((size_t)n + 64, 0);
     if (n)
         memcpy(in.data(), src, n);
-    IsecItem it = {};
-    it.src_len = n;
-    it.dst_cap = std::min<uint32_t>(limit, 0x7fffffffu);
-    it.tile0 = 0;
-    const bool act = n > cb;
-    it.ntiles = act ? (uint32_t)(((uint64_t)n + cb - 1u) / cb) : 0u;
-    std::vector<IsecTile> scan;
-    for (uint32_t k = 1; k < it.ntiles; k++)
-        scan.push_back(IsecTile{0u, k});
-    const size_t ch = std::max(1u, it.ntiles);
+    const uint64_t off0 = 0;
+    InfLayout L; /* the runtime's layout of a batch of this one stream, and its limit for a check plan's pieces */
+    chk_layout(1, &n, &off0, nullptr, &limit, cb, [](uint32_t) { return true; }, L);
+    L.items[0].dst_cap = std::min<uint32_t>(limit, 0x7fffffffu);
+    const bool act = L.pool != 0;
+    const size_t ch = std::max<size_t>(1, L.pool);
     uint32_t nsec1 = 0, active = 0, q[4] = {0, 0, 0, 0};
     IsecStream st;
     memset(&st, 0x5a, sizeof st);
@@ -65,32 +62,26 @@ static int check_one(const uint8_t *src, uint32_t n, int window_bits, uint32_t l
     std::vector<uint8_t> win(act ? ch * INF_WIN : 0, 0x5a);
     IchkPlan P;
     memset(&P, 0, sizeof P);
-    P.sp.items = &it;
-    P.sp.tiles = scan.data();
-    P.sp.nsec = &nsec1;
-    P.sp.st = &st;
-    P.sp.active = &active;
-    P.sp.q = q;
-    P.sp.cstop = cstop.data();
-    P.sp.clink = clink.data();
-    P.sp.clen = clen.data();
-    P.sp.chain_k = chain_k.data();
-    P.sp.chain_off = chain_off.data();
-    P.sp.chain_ck = chain_ck.data();
-    P.sp.count = 1;
-    P.sp.ntiles = (uint32_t)scan.size();
-    P.sp.pool = (uint32_t)ch;
-    P.sp.window_bits = window_bits;
-    P.sp.work_mul = SEC_WORK_MUL;
-    P.sp.work_add = SEC_WORK_ADD;
-    P.cand = cand.data();
-    P.cused = cused.data();
-    P.creach = creach.data();
-    P.want = want.data();
-    P.ring = ring.data();
-    P.win = win.data();
-    P.nactive = act ? 1u : 0u;
-    P.chunk_bytes = cb;
+    InfPlanMem m = {};
+    m.items = L.items.data();
+    m.tiles = L.tiles.data();
+    m.nsec = &nsec1;
+    m.st = &st;
+    m.active = &active;
+    m.q = q;
+    m.cstop = cstop.data();
+    m.clink = clink.data();
+    m.clen = clen.data();
+    m.chain_k = chain_k.data();
+    m.chain_off = chain_off.data();
+    m.chain_ck = chain_ck.data();
+    m.cand = cand.data();
+    m.cused = cused.data();
+    m.creach = creach.data();
+    m.want = want.data();
+    m.ring = ring.data();
+    m.win = win.data();
+    chk_plan_view(P, m, L, window_bits, cb);
 
     InfLds *lds = new_lds();
     InfSecInfo si;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../zsc_amd/csrc/inflate_sections.h"
+#include "../../zsc_amd/csrc/inflate_plan_layout.h"
 
 static uint32_t g_work_mul = SEC_WORK_MUL, g_work_add = SEC_WORK_ADD;
 /* the count pass's work bound (tests make it small to reach it with small streams) */
@@ -43,17 +44,12 @@ extern "C" int emu_sec_uncompress(const uint8_t *src, uint32_t n, int window_bit
     memcpy(in.data(), src, n);
     std::vector<uint8_t> out((size_t)cap + 64, 0xEE);
 
-    IsecItem it = {};
-    it.src_off = 0;
-    it.dst_off = 0;
-    it.src_len = n;
-    it.dst_cap = cap;
-    it.cap = n / SEC_CAND_DIV + SEC_CAND_MIN;
-    it.ntiles = (n + SEC_TILE - 1u) / SEC_TILE;
-    std::vector<IsecTile> tiles(std::max(1u, it.ntiles));
-    for (uint32_t t = 0; t < it.ntiles; t++)
-        tiles[t] = IsecTile{0u, t * SEC_TILE};
-    const size_t nt = tiles.size(), nc = g_pool ? g_pool : SEC_POOL_SLOTS((uint64_t)n);
+    const uint64_t off0 = 0;
+    InfLayout L; /* the runtime's layout of a batch of this one stream */
+    sec_layout(1, &n, &off0, &off0, &cap, L);
+    if (g_pool)
+        L.pool = g_pool;
+    const size_t nt = std::max<size_t>(1, L.tiles.size()), nc = L.pool;
     std::vector<uint32_t> tile_cnt(nt, 0x5a5a5a5au), tile_off(nt, 0x5a5a5a5au);
     uint32_t scount = 0, nsec1 = 0, active = 0x5a5a5a5au, q[4] = {0, 0, 0, 0};
     IsecStream st;
@@ -61,28 +57,24 @@ extern "C" int emu_sec_uncompress(const uint8_t *src, uint32_t n, int window_bit
     std::vector<uint32_t> cstart(nc, 0x5a5a5a5au), cstop(nc, 0x5a5a5a5au), clink(nc, 0x5a5a5a5au),
         clen(nc, 0x5a5a5a5au), chain_k(nc, 0x5a5a5a5au), chain_off(nc, 0x5a5a5a5au), chain_ck(nc, 0x5a5a5a5au);
     IsecPlan P;
-    P.items = &it;
-    P.tiles = tiles.data();
-    P.tile_cnt = tile_cnt.data();
-    P.tile_off = tile_off.data();
-    P.scount = &scount;
-    P.nsec = &nsec1;
-    P.st = &st;
-    P.active = &active;
-    P.q = q;
-    P.cstart = cstart.data();
-    P.cstop = cstop.data();
-    P.clink = clink.data();
-    P.clen = clen.data();
-    P.chain_k = chain_k.data();
-    P.chain_off = chain_off.data();
-    P.chain_ck = chain_ck.data();
-    P.count = 1;
-    P.ntiles = it.ntiles;
-    P.pool = (uint32_t)nc;
-    P.window_bits = window_bits;
-    P.work_mul = g_work_mul;
-    P.work_add = g_work_add;
+    InfPlanMem m = {};
+    m.items = L.items.data();
+    m.tiles = L.tiles.data();
+    m.tile_cnt = tile_cnt.data();
+    m.tile_off = tile_off.data();
+    m.scount = &scount;
+    m.nsec = &nsec1;
+    m.st = &st;
+    m.active = &active;
+    m.q = q;
+    m.cstart = cstart.data();
+    m.cstop = cstop.data();
+    m.clink = clink.data();
+    m.clen = clen.data();
+    m.chain_k = chain_k.data();
+    m.chain_off = chain_off.data();
+    m.chain_ck = chain_ck.data();
+    sec_plan_view(P, m, L, window_bits, g_work_mul, g_work_add);
 
     InfLds *lds = (InfLds *)malloc(sizeof(InfLds));
     memset(lds, 0x3C, sizeof(InfLds));

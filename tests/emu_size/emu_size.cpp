@@ -1,7 +1,7 @@
 /*
  * emu_size.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program that sizes streams with the size
  * path (zsc_amd/csrc/inflate_size.h) on the lane emulation (wave.h, -DZSC_WAVE_EMU), kernel by kernel
- * as the runtime enqueues them (zsc_hip_runtime.hip, size_enqueue): setup -> scan -> count -> want ->
+ * as the runtime enqueues them (zsc_hip_runtime.hip, chk_enqueue): setup -> scan -> count -> want ->
  * retry -> resolve -> finish for a stream longer than a chunk, then the whole-stream size decode for a
  * stream that did not finish.
  *
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../zsc_amd/csrc/inflate_size.h"
+#include "../../zsc_amd/csrc/inflate_plan_layout.h"
 
 static InfLds *new_lds()
 {
@@ -34,16 +35,10 @@ static int size_one(const uint8_t *src, uint32_t n, int window_bits, uint32_t li
     std::vector<uint8_t> in((size_t)n + 64, 0);
     if (n)
         memcpy(in.data(), src, n);
-    IsecItem it = {};
-    it.src_len = n;
-    it.dst_cap = limit;
-    it.tile0 = 0;
-    const bool act = n > cb;
-    it.ntiles = act ? (uint32_t)(((uint64_t)n + cb - 1u) / cb) : 0u;
-    std::vector<IsecTile> scan;
-    for (uint32_t k = 1; k < it.ntiles; k++)
-        scan.push_back(IsecTile{0u, k});
-    const size_t ch = std::max(1u, it.ntiles);
+    const uint64_t off0 = 0;
+    InfLayout L; /* the runtime's layout of a batch of this one stream */
+    chk_layout(1, &n, &off0, nullptr, &limit, cb, [](uint32_t) { return true; }, L);
+    const size_t ch = std::max<size_t>(1, L.pool);
     uint32_t nsec1 = 0, active = 0, q[4] = {0, 0, 0, 0};
     IsecStream st;
     memset(&st, 0x5a, sizeof st);
@@ -53,29 +48,23 @@ static int size_one(const uint8_t *src, uint32_t n, int window_bits, uint32_t li
     std::vector<uint64_t> cand(ch * INF_PC_CANDS, 0x5a5a5a5a5a5a5a5aull);
     IchkPlan P;
     memset(&P, 0, sizeof P); /* (no ring, no window, no slice check values) */
-    P.sp.items = &it;
-    P.sp.tiles = scan.data();
-    P.sp.nsec = &nsec1;
-    P.sp.st = &st;
-    P.sp.active = &active;
-    P.sp.q = q;
-    P.sp.cstop = cstop.data();
-    P.sp.clink = clink.data();
-    P.sp.clen = clen.data();
-    P.sp.chain_k = chain_k.data();
-    P.sp.chain_off = chain_off.data();
-    P.sp.count = 1;
-    P.sp.ntiles = (uint32_t)scan.size();
-    P.sp.pool = (uint32_t)ch;
-    P.sp.window_bits = window_bits;
-    P.sp.work_mul = SEC_WORK_MUL;
-    P.sp.work_add = SEC_WORK_ADD;
-    P.cand = cand.data();
-    P.cused = cused.data();
-    P.creach = creach.data();
-    P.want = want.data();
-    P.nactive = act ? 1u : 0u;
-    P.chunk_bytes = cb;
+    InfPlanMem m = {};
+    m.items = L.items.data();
+    m.tiles = L.tiles.data();
+    m.nsec = &nsec1;
+    m.st = &st;
+    m.active = &active;
+    m.q = q;
+    m.cstop = cstop.data();
+    m.clink = clink.data();
+    m.clen = clen.data();
+    m.chain_k = chain_k.data();
+    m.chain_off = chain_off.data();
+    m.cand = cand.data();
+    m.cused = cused.data();
+    m.creach = creach.data();
+    m.want = want.data();
+    chk_plan_view(P, m, L, window_bits, cb);
 
     InfLds *lds = new_lds();
     InfSecInfo si;

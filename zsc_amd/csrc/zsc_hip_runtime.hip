@@ -3541,38 +3541,53 @@ static uint32_t inflate_grid(uint32_t count)
     return std::max(1u, std::min(need, fill));
 }
 
+#include "inflate_plan_layout.h"
+
+enum InfPlanKind { INF_PLAIN, INF_SECTIONS, INF_RESYNC, INF_CHUNKS, INF_INDEXED, INF_SIZE, INF_CHECK };
+
 struct zsc_hip_inflate_plan {
+    /* a device buffer of the plan: it cannot be declared without joining `owned`, which destroy releases */
+    struct Buf : DevBuf {
+        explicit Buf(std::vector<DevBuf *> &owned) { owned.push_back(this); }
+    };
+    std::vector<DevBuf *> owned;
+    InfPlanKind kind = INF_PLAIN;
+    /* what a kind has, and with it which entry points serve it */
+    bool has_sections() const { return kind == INF_SECTIONS || kind == INF_RESYNC; } /* resync: a sections plan with more */
+    bool writes_nothing() const { return kind == INF_SIZE || kind == INF_CHECK; }    /* check: a size plan with more */
+    bool has_chunks() const { return kind == INF_CHUNKS || writes_nothing(); }       /* cp and the chunk records */
+    bool has_rings() const { return kind == INF_CHECK; }                             /* a ring per lane group, a value per stream */
+    bool counts_pieces() const { return kind != INF_PLAIN; } /* every other kind keeps d_nsec, a sections plan's */
     uint32_t count = 0;
     int32_t window_bits = 15;
-    DevBuf d_items, d_order, d_res, d_resume, d_pending;
-    /* sections plans only (inflate_sections.h) */
-    bool sections = false;
+    Buf d_items{owned}, d_order{owned}, d_res{owned}, d_resume{owned}, d_pending{owned};
+    /* sections plans (inflate_sections.h) */
     IsecPlan sp = {};
     uint64_t ncand_total = 0, scratch_bytes = 0;
-    DevBuf d_sitems, d_tiles, d_tile_cnt, d_tile_off, d_scount, d_nsec, d_sst, d_active, d_q;
-    DevBuf d_cstart, d_cstop, d_clink, d_clen, d_chain_k, d_chain_off, d_chain_ck;
-    /* chunks plans only (inflate_chunks.h; they also use the sections plan's buffers above) */
-    bool chunks = false;
+    Buf d_sitems{owned}, d_tiles{owned}, d_tile_cnt{owned}, d_tile_off{owned}, d_scount{owned}, d_nsec{owned},
+        d_sst{owned}, d_active{owned}, d_q{owned};
+    Buf d_cstart{owned}, d_cstop{owned}, d_clink{owned}, d_clen{owned}, d_chain_k{owned}, d_chain_off{owned},
+        d_chain_ck{owned};
+    /* chunks plans (inflate_chunks.h; they also use the sections plan's buffers above) */
     IchkPlan cp = {};
-    DevBuf d_cand, d_cused, d_creach, d_want, d_ring, d_win;
-    /* resync plans only (inflate_resync.h; sections plans with these buffers besides) */
-    bool resync = false;
+    Buf d_cand{owned}, d_cused{owned}, d_creach{owned}, d_want{owned}, d_ring{owned}, d_win{owned};
+    /* resync plans (inflate_resync.h; sections plans with these buffers besides) */
     IrsyPlan rp = {};
-    DevBuf d_cerr, d_chain_fl, d_rst;
-    /* indexed plans only (inflate_index.h; they also use d_sitems, d_sst, d_active, d_q, d_nsec, d_clen,
-     * d_chain_k, d_chain_ck, d_cand and d_win) */
-    /* size plans only (inflate_size.h; with chunks they use cp and the chunks plan's record buffers, never
+    Buf d_cerr{owned}, d_chain_fl{owned}, d_rst{owned};
+    /* size plans (inflate_size.h; with chunks they use cp and the chunks plan's record buffers, never
      * d_ring, d_win or d_chain_ck) */
-    bool size_only = false, size_ran = false;
-    /* check plans only (inflate_check.h): size plans (size_only is set, and relaunches are the size decode)
-     * whose first launch decodes into rings; with chunks they use every buffer of a chunks plan */
-    bool check = false;
+    bool size_ran = false;
+    /* check plans (inflate_check.h): size plans (relaunches are the size decode) whose first launch decodes
+     * into rings; with chunks they use every buffer of a chunks plan */
     uint32_t check_waves = 0; /* wavefronts of k_inflate_check: d_rings holds CHK_RING bytes for each lane group */
-    DevBuf d_rings, d_ckval;
-    bool indexed = false, idx_fixed = false;
+    Buf d_rings{owned}, d_ckval{owned};
+    /* indexed plans (inflate_index.h; they also use d_sitems, d_sst, d_active, d_q, d_nsec, d_clen,
+     * d_chain_k, d_chain_ck, d_cand and d_win) */
+    bool idx_fixed = false;
     IidxPlan ip = {};
     uint32_t idx_active = 0;
-    DevBuf d_sst0, d_q0, d_ipieces, d_iunits, d_ixs, d_idone, d_res0, d_resume0;
+    Buf d_sst0{owned}, d_q0{owned}, d_ipieces{owned}, d_iunits{owned}, d_ixs{owned}, d_idone{owned}, d_res0{owned},
+        d_resume0{owned};
     /* chunks plans with the index enabled: the records of the streams asked for since the last run */
     std::map<uint32_t, std::pair<std::vector<ZidxRec>, uint64_t>> idx_recs;
     const void *last_src = nullptr;
@@ -3582,7 +3597,50 @@ struct zsc_hip_inflate_plan {
     bool timed = false;
     /* packing (pack.h), off unless zsc_hip_inflate_plan_pack_enable was called */
     PackState pack;
+
+    /* a buffer beyond a plain plan's: its bytes are the plan's scratch */
+    bool scratch(DevBuf &b, uint64_t bytes)
+    {
+        scratch_bytes += bytes;
+        return b.ensure(bytes);
+    }
+    /* what sp and cp point into (null where the kind has no such buffer) */
+    InfPlanMem mem() const
+    {
+        return {d_sitems.p, d_tiles.p, d_tile_cnt.p, d_tile_off.p, d_scount.p, d_nsec.p, d_sst.p, d_active.p,
+                d_q.p, d_cstart.p, d_cstop.p, d_clink.p, d_clen.p, d_chain_k.p, d_chain_off.p, d_chain_ck.p,
+                d_cand.p, d_cused.p, d_creach.p, d_want.p, d_ring.p, d_win.p};
+    }
 };
+
+static void inflate_plan_release(zsc_hip_inflate_plan *pl)
+{
+    for (DevBuf *b : pl->owned)
+        b->release();
+}
+
+/* the error exit of the create functions once the plain plan exists */
+static ZlibReturn inflate_plan_fail(zsc_hip_inflate_plan **plan_out, ZlibReturn rc = Z_MEM_ERROR)
+{
+    zsc_hip_inflate_plan_destroy(*plan_out);
+    *plan_out = nullptr;
+    return rc;
+}
+
+/* the items, the tiles the scan visits and the active streams of a layout, uploaded */
+static bool inflate_layout_upload(zsc_hip_inflate_plan *pl, const InfLayout &L)
+{
+    bool ok = true;
+    if (!L.items.empty())
+        ok = hipMemcpy(pl->d_sitems.p, L.items.data(), sizeof(IsecItem) * L.items.size(), hipMemcpyHostToDevice) ==
+             hipSuccess;
+    if (ok && !L.tiles.empty())
+        ok = hipMemcpy(pl->d_tiles.p, L.tiles.data(), sizeof(IsecTile) * L.tiles.size(), hipMemcpyHostToDevice) ==
+             hipSuccess;
+    if (ok && !L.active.empty())
+        ok = hipMemcpy(pl->d_active.p, L.active.data(), 4 * L.active.size(), hipMemcpyHostToDevice) == hipSuccess;
+    return ok;
+}
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_create_ordered(zsc_hip_inflate_plan **plan_out, U32 count,
                                                   const U32 *source_lens,
@@ -3641,11 +3699,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_ordered(zsc_hip_inflate_plan *
                  hipSuccess;
     }
     if (!ok) {
-        pl->d_items.release();
-        pl->d_order.release();
-        pl->d_res.release();
-        pl->d_resume.release();
-        pl->d_pending.release();
+        inflate_plan_release(pl);
         delete pl;
         return Z_MEM_ERROR;
     }
@@ -3665,18 +3719,6 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create(zsc_hip_inflate_plan **plan_ou
                                                window_bits, Z_NULL);
 }
 
-static void inflate_plan_release(zsc_hip_inflate_plan *pl)
-{
-    for (DevBuf *b : {&pl->d_items, &pl->d_order, &pl->d_res, &pl->d_resume, &pl->d_pending, &pl->d_sitems,
-                      &pl->d_tiles, &pl->d_tile_cnt, &pl->d_tile_off, &pl->d_scount, &pl->d_nsec, &pl->d_sst,
-                      &pl->d_active, &pl->d_q, &pl->d_cstart, &pl->d_cstop, &pl->d_clink, &pl->d_clen,
-                      &pl->d_chain_k, &pl->d_chain_off, &pl->d_chain_ck, &pl->d_cand, &pl->d_cused, &pl->d_creach,
-                      &pl->d_want, &pl->d_ring, &pl->d_win, &pl->d_cerr, &pl->d_chain_fl, &pl->d_rst, &pl->d_sst0,
-                      &pl->d_q0, &pl->d_ipieces, &pl->d_iunits, &pl->d_ixs, &pl->d_idone, &pl->d_res0, &pl->d_resume0,
-                      &pl->d_rings, &pl->d_ckval})
-        b->release();
-}
-
 extern "C" ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan **plan_out, U32 count,
                                                            const U32 *source_lens,
                                                            const uint64_t *src_offsets,
@@ -3689,74 +3731,77 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan 
         return rc;
     DeviceScope scope;
     zsc_hip_inflate_plan *pl = *plan_out;
-    pl->sections = true;
-    /* per stream: its tiles of SEC_TILE input bytes; candidate records from one pool */
-    std::vector<IsecItem> items(count);
-    std::vector<IsecTile> tiles;
-    uint64_t total_in = 0;
-    for (U32 i = 0; i < count; i++) {
-        IsecItem &it = items[i];
-        it.src_off = src_offsets[i];
-        it.dst_off = dst_offsets[i];
-        it.src_len = source_lens[i];
-        it.dst_cap = dest_caps[i];
-        it.cap = source_lens[i] / SEC_CAND_DIV + SEC_CAND_MIN;
-        it.tile0 = (uint32_t)tiles.size();
-        it.ntiles = (source_lens[i] + SEC_TILE - 1u) / SEC_TILE;
-        it.pad = 0;
-        for (uint32_t t = 0; t < it.ntiles; t++)
-            tiles.push_back(IsecTile{i, t * SEC_TILE});
-        total_in += source_lens[i];
-    }
-    const uint64_t cand = std::min<uint64_t>(SEC_POOL_SLOTS(total_in), 0x0ffffff0u);
-    if (tiles.size() >= 0xffffffffull) {
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
-    }
-    const uint64_t nt = std::max<uint64_t>(1, tiles.size()), nc = std::max<uint64_t>(1, count);
+    pl->kind = INF_SECTIONS;
+    InfLayout L;
+    sec_layout(count, source_lens, src_offsets, dst_offsets, dest_caps, L);
+    if (L.tiles.size() >= 0xffffffffull)
+        return inflate_plan_fail(plan_out);
+    const uint64_t nt = std::max<uint64_t>(1, L.tiles.size()), nc = std::max<uint64_t>(1, count), cand = L.pool;
     pl->ncand_total = cand;
-    bool ok = pl->d_sitems.ensure(sizeof(IsecItem) * nc) && pl->d_tiles.ensure(sizeof(IsecTile) * nt) &&
-              pl->d_tile_cnt.ensure(4 * nt) && pl->d_tile_off.ensure(4 * nt) && pl->d_scount.ensure(4 * nc) &&
-              pl->d_nsec.ensure(4 * nc) && pl->d_sst.ensure(sizeof(IsecStream) * nc) &&
-              pl->d_active.ensure(4 * nc) && pl->d_q.ensure(16) && pl->d_cstart.ensure(4 * cand) &&
-              pl->d_cstop.ensure(4 * cand) && pl->d_clink.ensure(4 * cand) && pl->d_clen.ensure(4 * cand) &&
-              pl->d_chain_k.ensure(4 * cand) && pl->d_chain_off.ensure(4 * cand) && pl->d_chain_ck.ensure(4 * cand);
-    if (ok && count)
-        ok = hipMemcpy(pl->d_sitems.p, items.data(), sizeof(IsecItem) * count, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && !tiles.empty())
-        ok = hipMemcpy(pl->d_tiles.p, tiles.data(), sizeof(IsecTile) * tiles.size(), hipMemcpyHostToDevice) ==
-             hipSuccess;
-    if (!ok) {
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
+    bool ok = pl->scratch(pl->d_sitems, sizeof(IsecItem) * nc) && pl->scratch(pl->d_tiles, sizeof(IsecTile) * nt) &&
+              pl->scratch(pl->d_tile_cnt, 4 * nt) && pl->scratch(pl->d_tile_off, 4 * nt) &&
+              pl->scratch(pl->d_scount, 4 * nc) && pl->scratch(pl->d_nsec, 4 * nc) &&
+              pl->scratch(pl->d_sst, sizeof(IsecStream) * nc) && pl->scratch(pl->d_active, 4 * nc) &&
+              pl->scratch(pl->d_q, 16) && pl->scratch(pl->d_cstart, 4 * cand) && pl->scratch(pl->d_cstop, 4 * cand) &&
+              pl->scratch(pl->d_clink, 4 * cand) && pl->scratch(pl->d_clen, 4 * cand) &&
+              pl->scratch(pl->d_chain_k, 4 * cand) && pl->scratch(pl->d_chain_off, 4 * cand) &&
+              pl->scratch(pl->d_chain_ck, 4 * cand);
+    if (!ok || !inflate_layout_upload(pl, L))
+        return inflate_plan_fail(plan_out);
+    sec_plan_view(pl->sp, pl->mem(), L, window_bits);
+    return Z_OK;
+}
+
+/* what the chunk family (chunks, size and check plans) has beyond the plain plan, over the layout L of chunks
+ * of cb bytes: the sections plan's per-stream buffers, the candidates and the records of a chunk, and
+ * by kind the buffers of pieces that produce bytes */
+static ZlibReturn chunk_records_create(zsc_hip_inflate_plan **plan_out, U32 count, const InfLayout &L, uint32_t cb)
+{
+    zsc_hip_inflate_plan *pl = *plan_out;
+    const uint64_t nchunks = L.pool;
+    if (nchunks >= 0x03ffffffull) /* (links hold chunk * 4 + candidate in 28 bits) */
+        return inflate_plan_fail(plan_out);
+    const uint64_t nt = std::max<uint64_t>(1, L.tiles.size()), nc = std::max<uint64_t>(1, count);
+    const uint64_t ch = std::max<uint64_t>(1, nchunks);
+    /* the candidates and the records of a chunk */
+    bool ok = pl->scratch(pl->d_sitems, sizeof(IsecItem) * nc) && pl->scratch(pl->d_tiles, sizeof(IsecTile) * nt) &&
+              pl->scratch(pl->d_nsec, 4 * nc) && pl->scratch(pl->d_sst, sizeof(IsecStream) * nc) &&
+              pl->scratch(pl->d_active, 4 * nc) && pl->scratch(pl->d_q, 16) && pl->scratch(pl->d_cstop, 4 * ch) &&
+              pl->scratch(pl->d_clink, 4 * ch) && pl->scratch(pl->d_clen, 4 * ch) &&
+              pl->scratch(pl->d_chain_k, 4 * ch) && pl->scratch(pl->d_chain_off, 4 * ch) &&
+              pl->scratch(pl->d_cand, 8ull * INF_PC_CANDS * ch) && pl->scratch(pl->d_cused, 4 * ch) &&
+              pl->scratch(pl->d_creach, 4 * ch) && pl->scratch(pl->d_want, 4 * ch);
+    /* a size plan: no ring, no window, no slice check values.  A check plan has rings and windows for the
+     * streams with chunks only, 16 bytes behind each */
+    if (pl->kind == INF_CHUNKS)
+        ok = ok && pl->scratch(pl->d_chain_ck, 4 * ch) && pl->scratch(pl->d_ring, 2ull * INF_WIN * ch) &&
+             pl->scratch(pl->d_win, (uint64_t)INF_WIN * ch);
+    if (pl->has_rings()) {
+        /* ZSC_HIP_CHECK_GROUPS (a test hook): fewer lane groups, so that every ring is reused by several streams */
+        pl->check_waves = inflate_grid(count);
+        if (const char *e = getenv("ZSC_HIP_CHECK_GROUPS")) {
+            const long long g = atoll(e);
+            if (g > 0)
+                pl->check_waves = (uint32_t)std::min<long long>(pl->check_waves, (g + INF_PER_WAVE - 1) / INF_PER_WAVE);
+        }
+        ok = ok && pl->scratch(pl->d_chain_ck, 4 * ch) &&
+             pl->scratch(pl->d_ring, 2ull * INF_WIN * (nchunks ? ch : 0) + 16) &&
+             pl->scratch(pl->d_win, (uint64_t)INF_WIN * (nchunks ? ch : 0) + 16) &&
+             pl->scratch(pl->d_rings, (uint64_t)CHK_RING * pl->check_waves * INF_PER_WAVE) &&
+             pl->scratch(pl->d_ckval, 4 * nc);
     }
-    IsecPlan &P = pl->sp;
-    P.items = (const IsecItem *)pl->d_sitems.p;
-    P.tiles = (const IsecTile *)pl->d_tiles.p;
-    P.tile_cnt = (uint32_t *)pl->d_tile_cnt.p;
-    P.tile_off = (uint32_t *)pl->d_tile_off.p;
-    P.scount = (uint32_t *)pl->d_scount.p;
-    P.nsec = (uint32_t *)pl->d_nsec.p;
-    P.st = (IsecStream *)pl->d_sst.p;
-    P.active = (uint32_t *)pl->d_active.p;
-    P.q = (uint32_t *)pl->d_q.p;
-    P.cstart = (uint32_t *)pl->d_cstart.p;
-    P.cstop = (uint32_t *)pl->d_cstop.p;
-    P.clink = (uint32_t *)pl->d_clink.p;
-    P.clen = (uint32_t *)pl->d_clen.p;
-    P.chain_k = (uint32_t *)pl->d_chain_k.p;
-    P.chain_off = (uint32_t *)pl->d_chain_off.p;
-    P.chain_ck = (uint32_t *)pl->d_chain_ck.p;
-    P.count = count;
-    P.ntiles = (uint32_t)tiles.size();
-    P.pool = (uint32_t)cand;
-    P.window_bits = window_bits;
-    P.work_mul = SEC_WORK_MUL;
-    P.work_add = SEC_WORK_ADD;
-    pl->scratch_bytes = sizeof(IsecItem) * nc + (sizeof(IsecTile) + 8) * nt +
-                        (8 + sizeof(IsecStream) + 4) * nc + 16 + 28 * cand;
+    if (!ok || !inflate_layout_upload(pl, L))
+        return inflate_plan_fail(plan_out);
+    chk_plan_view(pl->cp, pl->mem(), L, pl->window_bits, cb);
+    pl->ncand_total = nchunks;
+    if (pl->has_rings()) {
+        /* the one figure that is not the sum of the allocations: a chunks plan's scratch for the streams with
+         * chunks (the chunks there are, not the one record allocated when there is none, and without the 16
+         * bytes behind the rings and windows), a ring per lane group, a value per stream */
+        pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
+                            (8ull * INF_PC_CANDS + 36 + 3ull * INF_WIN) * nchunks +
+                            (uint64_t)CHK_RING * pl->check_waves * INF_PER_WAVE + 4 * nc;
+    }
     return Z_OK;
 }
 
@@ -3770,90 +3815,14 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_chunks(zsc_hip_inflate_plan **
     if (rc != Z_OK)
         return rc;
     DeviceScope scope;
-    zsc_hip_inflate_plan *pl = *plan_out;
-    pl->chunks = true;
+    (*plan_out)->kind = INF_CHUNKS;
     const uint32_t cb = chunk_bytes == 0 ? CHK_DEFAULT_BYTES : std::max<uint32_t>(chunk_bytes, CHK_MIN_BYTES);
     /* per stream longer than a chunk (and with less than 2 GiB of output: positions inside a piece
      * are signed 32-bit): its chunks; the scan visits every chunk but the first */
-    std::vector<IsecItem> items(count);
-    std::vector<IsecTile> scan;
-    std::vector<uint32_t> active;
-    uint64_t nchunks = 0;
-    for (U32 i = 0; i < count; i++) {
-        IsecItem &it = items[i];
-        it.src_off = src_offsets[i];
-        it.dst_off = dst_offsets[i];
-        it.src_len = source_lens[i];
-        it.dst_cap = dest_caps[i];
-        it.cap = 0;
-        it.tile0 = (uint32_t)nchunks;
-        it.ntiles = 0;
-        it.pad = 0;
-        if (source_lens[i] > cb && dest_caps[i] < 0x80000000u) {
-            it.ntiles = (uint32_t)(((uint64_t)source_lens[i] + cb - 1u) / cb);
-            for (uint32_t k = 1; k < it.ntiles; k++)
-                scan.push_back(IsecTile{i, k});
-            active.push_back(i);
-            nchunks += it.ntiles;
-        }
-    }
-    if (nchunks >= 0x03ffffffull) { /* (links hold chunk * 4 + candidate in 28 bits) */
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
-    }
-    const uint64_t nt = std::max<uint64_t>(1, scan.size()), nc = std::max<uint64_t>(1, count);
-    const uint64_t ch = std::max<uint64_t>(1, nchunks);
-    bool ok = pl->d_sitems.ensure(sizeof(IsecItem) * nc) && pl->d_tiles.ensure(sizeof(IsecTile) * nt) &&
-              pl->d_nsec.ensure(4 * nc) && pl->d_sst.ensure(sizeof(IsecStream) * nc) && pl->d_active.ensure(4 * nc) &&
-              pl->d_q.ensure(16) && pl->d_cstop.ensure(4 * ch) && pl->d_clink.ensure(4 * ch) &&
-              pl->d_clen.ensure(4 * ch) && pl->d_chain_k.ensure(4 * ch) && pl->d_chain_off.ensure(4 * ch) &&
-              pl->d_chain_ck.ensure(4 * ch) && pl->d_cand.ensure(8ull * INF_PC_CANDS * ch) &&
-              pl->d_cused.ensure(4 * ch) && pl->d_creach.ensure(4 * ch) && pl->d_want.ensure(4 * ch) && pl->d_ring.ensure(2ull * INF_WIN * ch) &&
-              pl->d_win.ensure((uint64_t)INF_WIN * ch);
-    if (ok && count)
-        ok = hipMemcpy(pl->d_sitems.p, items.data(), sizeof(IsecItem) * count, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && !scan.empty())
-        ok = hipMemcpy(pl->d_tiles.p, scan.data(), sizeof(IsecTile) * scan.size(), hipMemcpyHostToDevice) ==
-             hipSuccess;
-    if (ok && !active.empty())
-        ok = hipMemcpy(pl->d_active.p, active.data(), 4 * active.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
-    }
-    IchkPlan &P = pl->cp;
-    P.sp.items = (const IsecItem *)pl->d_sitems.p;
-    P.sp.tiles = (const IsecTile *)pl->d_tiles.p;
-    P.sp.nsec = (uint32_t *)pl->d_nsec.p;
-    P.sp.st = (IsecStream *)pl->d_sst.p;
-    P.sp.active = (uint32_t *)pl->d_active.p;
-    P.sp.q = (uint32_t *)pl->d_q.p;
-    P.sp.cstop = (uint32_t *)pl->d_cstop.p;
-    P.sp.clink = (uint32_t *)pl->d_clink.p;
-    P.sp.clen = (uint32_t *)pl->d_clen.p;
-    P.sp.chain_k = (uint32_t *)pl->d_chain_k.p;
-    P.sp.chain_off = (uint32_t *)pl->d_chain_off.p;
-    P.sp.chain_ck = (uint32_t *)pl->d_chain_ck.p;
-    P.sp.count = count;
-    P.sp.ntiles = (uint32_t)scan.size();
-    P.sp.pool = (uint32_t)nchunks;
-    P.sp.window_bits = window_bits;
-    P.sp.work_mul = SEC_WORK_MUL;
-    P.sp.work_add = SEC_WORK_ADD;
-    P.cand = (uint64_t *)pl->d_cand.p;
-    P.cused = (uint32_t *)pl->d_cused.p;
-    P.creach = (uint32_t *)pl->d_creach.p;
-    P.want = (uint32_t *)pl->d_want.p;
-    P.ring = (uint16_t *)pl->d_ring.p;
-    P.win = (uint8_t *)pl->d_win.p;
-    P.nactive = (uint32_t)active.size();
-    P.chunk_bytes = cb;
-    pl->ncand_total = nchunks;
-    pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
-                        (8ull * INF_PC_CANDS + 36 + 3ull * INF_WIN) * ch;
-    return Z_OK;
+    InfLayout L;
+    chk_layout(count, source_lens, src_offsets, dst_offsets, dest_caps, cb,
+               [&](U32 i) { return dest_caps[i] < 0x80000000u; }, L);
+    return chunk_records_create(plan_out, count, L, cb);
 }
 
 /* a size plan, or (check) a check plan: the same items, queue order and chunk records, and for a check plan
@@ -3878,111 +3847,19 @@ static ZlibReturn size_plan_create(zsc_hip_inflate_plan **plan_out, U32 count, c
     if (rc != Z_OK)
         return rc;
     DeviceScope scope;
-    zsc_hip_inflate_plan *pl = *plan_out;
-    pl->size_only = true;
-    pl->check = check;
+    (*plan_out)->kind = check ? INF_CHECK : INF_SIZE;
     const uint32_t cb = chunk_bytes == 0 ? CHK_DEFAULT_BYTES : std::max<uint32_t>(chunk_bytes, CHK_MIN_BYTES);
     /* per stream longer than a chunk: its chunks; the scan visits every chunk but the first (any limit
      * will do: a piece is only counted, no position inside it is ever signed) */
-    std::vector<IsecItem> items(count);
-    std::vector<IsecTile> scan;
-    std::vector<uint32_t> active;
-    uint64_t nchunks = 0;
-    for (U32 i = 0; i < count; i++) {
-        IsecItem &it = items[i];
-        it.src_off = src_offsets[i];
-        it.dst_off = 0;
-        it.src_len = source_lens[i];
-        /* (a check plan's pieces sign positions in 32 bits, as a chunks plan's: a stream of 2 GiB or more is
-         * left to the whole-stream decode by this limit) */
-        it.dst_cap = check ? std::min<uint32_t>(limits[i], 0x7fffffffu) : limits[i];
-        it.cap = 0;
-        it.tile0 = (uint32_t)nchunks;
-        it.ntiles = 0;
-        it.pad = 0;
-        if (chunk_bytes != 0xffffffffu && source_lens[i] > cb) {
-            it.ntiles = (uint32_t)(((uint64_t)source_lens[i] + cb - 1u) / cb);
-            for (uint32_t k = 1; k < it.ntiles; k++)
-                scan.push_back(IsecTile{i, k});
-            active.push_back(i);
-            nchunks += it.ntiles;
-        }
-    }
-    if (nchunks >= 0x03ffffffull) { /* (links hold chunk * 4 + candidate in 28 bits) */
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
-    }
-    const uint64_t nt = std::max<uint64_t>(1, scan.size()), nc = std::max<uint64_t>(1, count);
-    const uint64_t ch = std::max<uint64_t>(1, nchunks);
-    /* the candidates and the records of a chunk; no ring, no window, no slice check values */
-    bool ok = pl->d_sitems.ensure(sizeof(IsecItem) * nc) && pl->d_tiles.ensure(sizeof(IsecTile) * nt) &&
-              pl->d_nsec.ensure(4 * nc) && pl->d_sst.ensure(sizeof(IsecStream) * nc) && pl->d_active.ensure(4 * nc) &&
-              pl->d_q.ensure(16) && pl->d_cstop.ensure(4 * ch) && pl->d_clink.ensure(4 * ch) &&
-              pl->d_clen.ensure(4 * ch) && pl->d_chain_k.ensure(4 * ch) && pl->d_chain_off.ensure(4 * ch) &&
-              pl->d_cand.ensure(8ull * INF_PC_CANDS * ch) && pl->d_cused.ensure(4 * ch) &&
-              pl->d_creach.ensure(4 * ch) && pl->d_want.ensure(4 * ch);
-    if (check) {
-        /* ZSC_HIP_CHECK_GROUPS (a test hook): fewer lane groups, so that every ring is reused by several streams */
-        pl->check_waves = inflate_grid(count);
-        if (const char *e = getenv("ZSC_HIP_CHECK_GROUPS")) {
-            const long long g = atoll(e);
-            if (g > 0)
-                pl->check_waves = (uint32_t)std::min<long long>(pl->check_waves, (g + INF_PER_WAVE - 1) / INF_PER_WAVE);
-        }
-        ok = ok && pl->d_chain_ck.ensure(4 * ch) && pl->d_ring.ensure(2ull * INF_WIN * (nchunks ? ch : 0) + 16) &&
-             pl->d_win.ensure((uint64_t)INF_WIN * (nchunks ? ch : 0) + 16) &&
-             pl->d_rings.ensure((uint64_t)CHK_RING * pl->check_waves * INF_PER_WAVE) && pl->d_ckval.ensure(4 * nc);
-    }
-    if (ok && count)
-        ok = hipMemcpy(pl->d_sitems.p, items.data(), sizeof(IsecItem) * count, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && !scan.empty())
-        ok = hipMemcpy(pl->d_tiles.p, scan.data(), sizeof(IsecTile) * scan.size(), hipMemcpyHostToDevice) ==
-             hipSuccess;
-    if (ok && !active.empty())
-        ok = hipMemcpy(pl->d_active.p, active.data(), 4 * active.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
-    }
-    IchkPlan &P = pl->cp;
-    P.sp.items = (const IsecItem *)pl->d_sitems.p;
-    P.sp.tiles = (const IsecTile *)pl->d_tiles.p;
-    P.sp.nsec = (uint32_t *)pl->d_nsec.p;
-    P.sp.st = (IsecStream *)pl->d_sst.p;
-    P.sp.active = (uint32_t *)pl->d_active.p;
-    P.sp.q = (uint32_t *)pl->d_q.p;
-    P.sp.cstop = (uint32_t *)pl->d_cstop.p;
-    P.sp.clink = (uint32_t *)pl->d_clink.p;
-    P.sp.clen = (uint32_t *)pl->d_clen.p;
-    P.sp.chain_k = (uint32_t *)pl->d_chain_k.p;
-    P.sp.chain_off = (uint32_t *)pl->d_chain_off.p;
-    P.sp.count = count;
-    P.sp.ntiles = (uint32_t)scan.size();
-    P.sp.pool = (uint32_t)nchunks;
-    P.sp.window_bits = window_bits;
-    P.sp.work_mul = SEC_WORK_MUL;
-    P.sp.work_add = SEC_WORK_ADD;
-    P.cand = (uint64_t *)pl->d_cand.p;
-    P.cused = (uint32_t *)pl->d_cused.p;
-    P.creach = (uint32_t *)pl->d_creach.p;
-    P.want = (uint32_t *)pl->d_want.p;
-    P.nactive = (uint32_t)active.size();
-    P.chunk_bytes = cb;
-    pl->ncand_total = nchunks;
-    pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
-                        (8ull * INF_PC_CANDS + 32) * ch;
-    if (check) {
-        P.sp.chain_ck = (uint32_t *)pl->d_chain_ck.p;
-        P.ring = (uint16_t *)pl->d_ring.p;
-        P.win = (uint8_t *)pl->d_win.p;
-        /* a chunks plan's scratch for the streams with chunks, a ring per lane group, a value per stream */
-        pl->scratch_bytes = (sizeof(IsecItem) + sizeof(IsecStream) + 8) * nc + 16 + sizeof(IsecTile) * nt +
-                            (8ull * INF_PC_CANDS + 36 + 3ull * INF_WIN) * nchunks +
-                            (uint64_t)CHK_RING * pl->check_waves * INF_PER_WAVE + 4 * nc;
-    }
-    return Z_OK;
+    InfLayout L;
+    chk_layout(count, source_lens, src_offsets, nullptr, limits.data(), cb,
+               [&](U32) { return chunk_bytes != 0xffffffffu; }, L);
+    /* (a check plan's pieces sign positions in 32 bits, as a chunks plan's: a stream of 2 GiB or more is
+     * left to the whole-stream decode by this limit) */
+    if (check)
+        for (IsecItem &it : L.items)
+            it.dst_cap = std::min<uint32_t>(it.dst_cap, 0x7fffffffu);
+    return chunk_records_create(plan_out, count, L, cb);
 }
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_create_size(zsc_hip_inflate_plan **plan_out, U32 count,
@@ -4010,19 +3887,16 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_resync(zsc_hip_inflate_plan **
         return rc;
     DeviceScope scope;
     zsc_hip_inflate_plan *pl = *plan_out;
-    pl->resync = true;
+    pl->kind = INF_RESYNC;
     const uint64_t cand = pl->ncand_total, nc = std::max(1u, count);
-    if (!pl->d_cerr.ensure(8 * cand) || !pl->d_chain_fl.ensure(4 * cand) || !pl->d_rst.ensure(sizeof(IrsyStream) * nc)) {
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
-    }
+    if (!pl->scratch(pl->d_cerr, 8 * cand) || !pl->scratch(pl->d_chain_fl, 4 * cand) ||
+        !pl->scratch(pl->d_rst, sizeof(IrsyStream) * nc))
+        return inflate_plan_fail(plan_out);
     IrsyPlan &R = pl->rp;
     R.sp = pl->sp;
     R.cerr = (uint64_t *)pl->d_cerr.p;
     R.chain_fl = (uint32_t *)pl->d_chain_fl.p;
     R.rst = (IrsyStream *)pl->d_rst.p;
-    pl->scratch_bytes += 12 * cand + sizeof(IrsyStream) * nc;
     return Z_OK;
 }
 
@@ -4055,7 +3929,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_indexed(zsc_hip_inflate_plan *
         return rc;
     DeviceScope scope;
     zsc_hip_inflate_plan *pl = *plan_out;
-    pl->indexed = true;
+    pl->kind = INF_INDEXED;
     pl->idx_fixed = B.any_fixed;
     pl->idx_active = (uint32_t)B.active.size();
     const uint64_t nc = std::max<uint64_t>(1, count), np = std::max<uint64_t>(1, B.pieces.size());
@@ -4091,18 +3965,13 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_indexed(zsc_hip_inflate_plan *
         {&pl->d_win, B.win.data(), B.win.size(), B.win.size()},
     };
     bool ok = true;
-    pl->scratch_bytes = 0;
     for (const Up &u : ups) {
-        ok = ok && u.buf->ensure(u.bytes);
+        ok = ok && pl->scratch(*u.buf, u.bytes);
         if (ok && u.have)
             ok = hipMemcpy(u.buf->p, u.from, u.have, hipMemcpyHostToDevice) == hipSuccess;
-        pl->scratch_bytes += u.bytes;
     }
-    if (!ok) {
-        zsc_hip_inflate_plan_destroy(pl);
-        *plan_out = nullptr;
-        return Z_MEM_ERROR;
-    }
+    if (!ok)
+        return inflate_plan_fail(plan_out);
     IidxPlan &P = pl->ip;
     P.sp.items = (const IsecItem *)pl->d_sitems.p;
     P.sp.nsec = (uint32_t *)pl->d_nsec.p;
@@ -4125,6 +3994,24 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_indexed(zsc_hip_inflate_plan *
     return Z_OK;
 }
 
+/* the grids of a plan's launches ahead of the whole-stream decode, worked out once per run from the streams
+ * that may take part, the records (candidates, chunks or units) lane groups take from a queue, and the
+ * tiles the scan visits */
+struct InfGrid {
+    uint32_t fill;       /* wavefronts that fill the device */
+    uint32_t per_stream; /* a wavefront for each stream */
+    uint32_t per_group;  /* a lane group for each stream */
+    uint32_t groups;     /* a lane group for each record */
+    uint32_t scans;      /* a wavefront for each tile */
+    InfGrid(uint32_t streams, uint64_t records, uint32_t tiles)
+        : fill((uint32_t)g_cus * 4u * INF_WAVES_EU), per_stream(std::max(1u, std::min(streams, fill))),
+          per_group((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE),
+          groups((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (records + INF_PER_WAVE - 1) / INF_PER_WAVE))),
+          scans(std::max(1u, std::min(tiles, fill * 4u)))
+    {
+    }
+};
+
 /* the launches of an indexed plan, ahead of k_inflate: the state every run starts from, the write
  * pass, finish */
 static ZlibReturn idx_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
@@ -4144,136 +4031,95 @@ static ZlibReturn idx_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void 
     HIP_TRY(hipMemcpyAsync(pl->d_sst.p, pl->d_sst0.p, sizeof(IsecStream) * pl->count, hipMemcpyDeviceToDevice, st),
             return Z_STREAM_ERROR);
     HIP_TRY(hipMemcpyAsync(pl->d_q.p, pl->d_q0.p, 16, hipMemcpyDeviceToDevice, st), return Z_STREAM_ERROR);
-    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
-    const uint32_t groups = std::max(1u, std::min(fill, (P.nunits + INF_PER_WAVE - 1) / INF_PER_WAVE));
-    hipLaunchKernelGGL(k_idx_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P,
+    const InfGrid g(pl->idx_active, P.nunits, 0);
+    hipLaunchKernelGGL(k_idx_write, dim3(g.groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P,
                        (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
-    if (pl->idx_active) {
-        const uint32_t per_stream = std::max(1u, std::min(pl->idx_active, fill));
-        hipLaunchKernelGGL(k_sec_finish, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
-                           (const uint8_t *)d_src, P.sp, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
-    }
+    if (pl->idx_active)
+        hipLaunchKernelGGL(k_sec_finish, dim3(g.per_group), dim3(64), 0, st, (const uint8_t *)d_src, P.sp,
+                           (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
     return Z_OK;
 }
 
-/* the launches of a chunks plan, ahead of k_inflate (none when no stream is longer than a chunk) */
+/* the launches of the chunk family ahead of the whole-stream decode (none when no stream is longer than a
+ * chunk).  A chunks plan: setup, scan, count, want, retry, resolve, window, write, finish.  A size plan: the
+ * same without the window and write passes, with its own count, retry, resolve and finish.  A check plan: a
+ * chunks plan's with the check-write pass for the write pass and the values copied out behind finish. */
 static void chk_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
 {
     const IchkPlan &P = pl->cp;
     if (P.nactive == 0)
         return;
-    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
-    const uint32_t per_stream = std::max(1u, std::min(P.nactive, fill));
-    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
-    const uint32_t scans = std::max(1u, std::min(P.sp.ntiles, fill * 4u));
-    hipLaunchKernelGGL(k_chk_setup, dim3(per_stream), dim3(64), 0, st, P);
-    hipLaunchKernelGGL(k_chk_scan, dim3(scans), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_chk_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_chk_want, dim3(per_stream), dim3(64), 0, st, P);
-    hipLaunchKernelGGL(k_chk_retry, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_chk_resolve, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
-                       (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_chk_window, dim3(std::min<uint32_t>(P.nactive, (uint32_t)g_cus * 4u)), dim3(CHK_WINDOW_THREADS), 0, st, P);
-    hipLaunchKernelGGL(k_chk_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P);
-    hipLaunchKernelGGL(k_sec_finish, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
-                       (const uint8_t *)d_src, P.sp, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
-}
-
-/* the launches of a size plan's chunked path, ahead of k_inflate_size (none when no stream is longer
- * than a chunk): the chunks plan's without the window and write passes */
-static void size_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, hipStream_t st)
-{
-    const IchkPlan &P = pl->cp;
-    if (P.nactive == 0)
+    const uint8_t *src = (const uint8_t *)d_src;
+    InfResult *res = (InfResult *)pl->d_res.p;
+    InfResume *resume = (InfResume *)pl->d_resume.p;
+    const bool size = pl->kind == INF_SIZE;
+    const InfGrid g(P.nactive, pl->ncand_total, P.sp.ntiles);
+    hipLaunchKernelGGL(k_chk_setup, dim3(g.per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_chk_scan, dim3(g.scans), dim3(64), 0, st, src, P);
+    hipLaunchKernelGGL(size ? k_size_count : k_chk_count, dim3(g.groups), dim3(64), 0, st, src, P);
+    hipLaunchKernelGGL(k_chk_want, dim3(g.per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(size ? k_size_retry : k_chk_retry, dim3(g.groups), dim3(64), 0, st, src, P);
+    hipLaunchKernelGGL(size ? k_size_resolve : k_chk_resolve, dim3(g.per_group), dim3(64), 0, st, src, P);
+    if (size) {
+        hipLaunchKernelGGL(k_size_finish, dim3(g.per_group), dim3(64), 0, st, src, P, res, resume);
         return;
-    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
-    const uint32_t per_stream = std::max(1u, std::min(P.nactive, fill));
-    const uint32_t per_group = (per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE;
-    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
-    const uint32_t scans = std::max(1u, std::min(P.sp.ntiles, fill * 4u));
-    hipLaunchKernelGGL(k_chk_setup, dim3(per_stream), dim3(64), 0, st, P);
-    hipLaunchKernelGGL(k_chk_scan, dim3(scans), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_size_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_chk_want, dim3(per_stream), dim3(64), 0, st, P);
-    hipLaunchKernelGGL(k_size_retry, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_size_resolve, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_size_finish, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P,
-                       (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
-}
-
-static void size_launch(zsc_hip_inflate_plan *pl, const void *d_src, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_inflate_size, dim3(inflate_grid(pl->count)), dim3(64), 0, st, (const uint8_t *)d_src,
-                       (const ZdInfItem *)pl->d_items.p, (const uint32_t *)pl->d_order.p, (InfResult *)pl->d_res.p,
-                       (InfResume *)pl->d_resume.p, (uint32_t *)pl->d_pending.p, pl->window_bits, pl->count);
-}
-
-/* the launches of a check plan: the chunks plan's (none when no stream is longer than a chunk) with the
- * check-write pass for the write pass and the values copied out behind k_sec_finish, then k_inflate_check */
-static void check_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, hipStream_t st)
-{
-    const IchkPlan &P = pl->cp;
-    if (P.nactive != 0) {
-        const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
-        const uint32_t per_stream = std::max(1u, std::min(P.nactive, fill));
-        const uint32_t per_group = (per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE;
-        const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
-        const uint32_t scans = std::max(1u, std::min(P.sp.ntiles, fill * 4u));
-        hipLaunchKernelGGL(k_chk_setup, dim3(per_stream), dim3(64), 0, st, P);
-        hipLaunchKernelGGL(k_chk_scan, dim3(scans), dim3(64), 0, st, (const uint8_t *)d_src, P);
-        hipLaunchKernelGGL(k_chk_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-        hipLaunchKernelGGL(k_chk_want, dim3(per_stream), dim3(64), 0, st, P);
-        hipLaunchKernelGGL(k_chk_retry, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-        hipLaunchKernelGGL(k_chk_resolve, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P);
-        hipLaunchKernelGGL(k_chk_window, dim3(std::min<uint32_t>(P.nactive, (uint32_t)g_cus * 4u)), dim3(CHK_WINDOW_THREADS), 0, st, P);
-        hipLaunchKernelGGL(k_check_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-        hipLaunchKernelGGL(k_sec_finish, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, P.sp,
-                           (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
-        hipLaunchKernelGGL(k_check_finish, dim3(per_group), dim3(64), 0, st, P, (const InfResume *)pl->d_resume.p,
-                           (uint32_t *)pl->d_ckval.p);
     }
-    hipLaunchKernelGGL(k_inflate_check, dim3(pl->check_waves), dim3(64), 0, st, (const uint8_t *)d_src,
-                       (uint8_t *)pl->d_rings.p, (const ZdInfItem *)pl->d_items.p, (const uint32_t *)pl->d_order.p,
-                       (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p, (uint32_t *)pl->d_ckval.p,
-                       (uint32_t *)pl->d_pending.p, pl->window_bits, pl->count);
+    hipLaunchKernelGGL(k_chk_window, dim3(std::min<uint32_t>(P.nactive, (uint32_t)g_cus * 4u)), dim3(CHK_WINDOW_THREADS), 0, st, P);
+    if (pl->has_rings())
+        hipLaunchKernelGGL(k_check_write, dim3(g.groups), dim3(64), 0, st, src, P);
+    else
+        hipLaunchKernelGGL(k_chk_write, dim3(g.groups), dim3(64), 0, st, src, (uint8_t *)d_dst, P);
+    hipLaunchKernelGGL(k_sec_finish, dim3(g.per_group), dim3(64), 0, st, src, P.sp, res, resume);
+    if (pl->has_rings())
+        hipLaunchKernelGGL(k_check_finish, dim3(g.per_group), dim3(64), 0, st, P, (const InfResume *)resume,
+                           (uint32_t *)pl->d_ckval.p);
 }
 
-/* the launches of a resync plan, ahead of k_inflate: the sections plan's scan and setup, then its own */
-static void rsy_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
-{
-    const IrsyPlan &R = pl->rp;
-    const IsecPlan &P = R.sp;
-    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU;
-    const uint32_t per_stream = std::max(1u, std::min(pl->count, fill));
-    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
-    const uint32_t tiles = std::max(1u, std::min(P.ntiles, fill * 4u));
-    const uint32_t per_group = (per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE;
-    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 0);
-    hipLaunchKernelGGL(k_sec_setup, dim3(per_stream), dim3(64), 0, st, P);
-    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 1);
-    hipLaunchKernelGGL(k_rsy_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, R);
-    hipLaunchKernelGGL(k_rsy_resolve, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, R);
-    hipLaunchKernelGGL(k_rsy_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, R);
-    hipLaunchKernelGGL(k_rsy_finish, dim3(per_group), dim3(64), 0, st, (const uint8_t *)d_src, R,
-                       (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
-}
-
-/* the six launches of a sections plan, ahead of k_inflate */
+/* the launches of a sections plan, ahead of k_inflate: scan, setup, scan again, then count, resolve, write and
+ * finish -- a resync plan's own (which take R), or the sections plan's */
 static void sec_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
 {
+    const IrsyPlan &R = pl->rp;
     const IsecPlan &P = pl->sp;
-    const uint32_t fill = (uint32_t)g_cus * 4u * INF_WAVES_EU; /* wavefronts that fill the device */
-    const uint32_t per_stream = std::max(1u, std::min(pl->count, fill));
-    const uint32_t groups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fill, (pl->ncand_total + INF_PER_WAVE - 1) / INF_PER_WAVE));
-    const uint32_t tiles = std::max(1u, std::min(P.ntiles, fill * 4u));
-    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 0);
-    hipLaunchKernelGGL(k_sec_setup, dim3(per_stream), dim3(64), 0, st, P);
-    hipLaunchKernelGGL(k_sec_scan, dim3(tiles), dim3(64), 0, st, (const uint8_t *)d_src, P, 1);
-    hipLaunchKernelGGL(k_sec_count, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, P);
-    hipLaunchKernelGGL(k_sec_resolve, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st, P);
-    hipLaunchKernelGGL(k_sec_write, dim3(groups), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, P);
-    hipLaunchKernelGGL(k_sec_finish, dim3((per_stream + INF_PER_WAVE - 1) / INF_PER_WAVE), dim3(64), 0, st,
-                       (const uint8_t *)d_src, P, (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p);
+    const uint8_t *src = (const uint8_t *)d_src;
+    InfResult *res = (InfResult *)pl->d_res.p;
+    InfResume *resume = (InfResume *)pl->d_resume.p;
+    const InfGrid g(pl->count, pl->ncand_total, P.ntiles);
+    hipLaunchKernelGGL(k_sec_scan, dim3(g.scans), dim3(64), 0, st, src, P, 0);
+    hipLaunchKernelGGL(k_sec_setup, dim3(g.per_stream), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(k_sec_scan, dim3(g.scans), dim3(64), 0, st, src, P, 1);
+    if (pl->kind == INF_RESYNC) {
+        hipLaunchKernelGGL(k_rsy_count, dim3(g.groups), dim3(64), 0, st, src, R);
+        hipLaunchKernelGGL(k_rsy_resolve, dim3(g.per_group), dim3(64), 0, st, src, R);
+        hipLaunchKernelGGL(k_rsy_write, dim3(g.groups), dim3(64), 0, st, src, (uint8_t *)d_dst, R);
+        hipLaunchKernelGGL(k_rsy_finish, dim3(g.per_group), dim3(64), 0, st, src, R, res, resume);
+    } else {
+        hipLaunchKernelGGL(k_sec_count, dim3(g.groups), dim3(64), 0, st, src, P);
+        hipLaunchKernelGGL(k_sec_resolve, dim3(g.per_group), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(k_sec_write, dim3(g.groups), dim3(64), 0, st, src, (uint8_t *)d_dst, P);
+        hipLaunchKernelGGL(k_sec_finish, dim3(g.per_group), dim3(64), 0, st, src, P, res, resume);
+    }
+}
+
+/* the whole-stream decode of what the launches above left: the first launch of a run, and every relaunch of
+ * _results.  A check plan's first launch decodes into the rings; its relaunches are the size decode. */
+static void inflate_launch(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st, bool first)
+{
+    const uint8_t *src = (const uint8_t *)d_src;
+    const ZdInfItem *items = (const ZdInfItem *)pl->d_items.p;
+    const uint32_t *order = (const uint32_t *)pl->d_order.p;
+    InfResult *res = (InfResult *)pl->d_res.p;
+    InfResume *resume = (InfResume *)pl->d_resume.p;
+    uint32_t *pending = (uint32_t *)pl->d_pending.p;
+    if (pl->has_rings() && first)
+        hipLaunchKernelGGL(k_inflate_check, dim3(pl->check_waves), dim3(64), 0, st, src, (uint8_t *)pl->d_rings.p, items,
+                           order, res, resume, (uint32_t *)pl->d_ckval.p, pending, pl->window_bits, pl->count);
+    else if (pl->writes_nothing())
+        hipLaunchKernelGGL(k_inflate_size, dim3(inflate_grid(pl->count)), dim3(64), 0, st, src, items, order, res,
+                           resume, pending, pl->window_bits, pl->count);
+    else
+        hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, st, src, (uint8_t *)d_dst, items, order,
+                           res, resume, pending, pl->window_bits, pl->count);
 }
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const void *d_src,
@@ -4290,51 +4136,29 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
     pl->last_dst = d_dst;
     HIP_TRY(hipMemsetAsync(pl->d_resume.p, 0, sizeof(InfResume) * pl->count, st), return Z_STREAM_ERROR);
     HIP_TRY(hipMemsetAsync(pl->d_pending.p, 0, 8, st), return Z_STREAM_ERROR); /* [0] streams to relaunch, [1] the queue */
-    if (pl->sections) {
+    if (pl->has_sections())
         HIP_TRY(hipMemsetAsync(pl->d_scount.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+    if (pl->has_sections() || pl->has_chunks()) { /* (an indexed plan sets these up itself) */
         HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
         HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
     }
-    if (pl->chunks) {
-        HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
-        HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
-    }
-    if (pl->size_only) {
+    if (pl->writes_nothing()) {
         /* nothing is written through d_dst: it is not looked at */
         pl->last_dst = nullptr;
         pl->size_ran = true;
-        HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
-        HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
-        if (pl->check)
-            HIP_TRY(hipMemsetAsync(pl->d_ckval.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
-        (void)hipEventRecord(pl->ev0, st);
-        if (pl->check) {
-            check_enqueue(pl, d_src, st);
-        } else {
-            size_enqueue(pl, d_src, st);
-            size_launch(pl, d_src, st);
-        }
-        (void)hipEventRecord(pl->ev1, st);
-        pl->timed = true;
-        HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
-        return Z_OK;
     }
+    if (pl->has_rings())
+        HIP_TRY(hipMemsetAsync(pl->d_ckval.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
     (void)hipEventRecord(pl->ev0, st);
-    if (pl->resync)
-        rsy_enqueue(pl, d_src, d_dst, st);
-    else if (pl->sections)
+    if (pl->has_sections())
         sec_enqueue(pl, d_src, d_dst, st);
-    if (pl->chunks) {
+    if (pl->kind == INF_CHUNKS)
         pl->idx_recs.clear();
+    if (pl->has_chunks())
         chk_enqueue(pl, d_src, d_dst, st);
-    }
-    if (pl->indexed && idx_enqueue(pl, d_src, d_dst, st) != Z_OK)
+    if (pl->kind == INF_INDEXED && idx_enqueue(pl, d_src, d_dst, st) != Z_OK)
         return Z_STREAM_ERROR;
-    hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, st, (const uint8_t *)d_src,
-                       (uint8_t *)d_dst, (const ZdInfItem *)pl->d_items.p,
-                       (const uint32_t *)pl->d_order.p, (InfResult *)pl->d_res.p,
-                       (InfResume *)pl->d_resume.p, (uint32_t *)pl->d_pending.p, pl->window_bits,
-                       pl->count);
+    inflate_launch(pl, d_src, d_dst, st, true);
     (void)hipEventRecord(pl->ev1, st);
     pl->timed = true;
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
@@ -4356,16 +4180,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_results(zsc_hip_inflate_plan *pl, U32
         if (pending == 0 || round > (1u << 30))
             break;
         HIP_TRY(hipMemsetAsync(pl->d_pending.p, 0, 8, pl->last_stream), return Z_STREAM_ERROR);
-        if (pl->size_only) {
-            size_launch(pl, pl->last_src, pl->last_stream);
-            HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
-            continue;
-        }
-        hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, pl->last_stream,
-                           (const uint8_t *)pl->last_src, (uint8_t *)pl->last_dst,
-                           (const ZdInfItem *)pl->d_items.p, (const uint32_t *)pl->d_order.p,
-                           (InfResult *)pl->d_res.p, (InfResume *)pl->d_resume.p,
-                           (uint32_t *)pl->d_pending.p, pl->window_bits, pl->count);
+        inflate_launch(pl, pl->last_src, pl->last_dst, pl->last_stream, false);
         HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
     }
     std::vector<InfResult> res(pl->count);
@@ -4413,7 +4228,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U3
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     ZSC_ASSERT(sections != Z_NULL);
-    if (!(pl->sections || pl->chunks || pl->indexed || pl->size_only) || !(pl->last_dst || pl->size_ran) ||
+    if (!pl->counts_pieces() || !(pl->last_dst || pl->size_ran) ||
         pl->count == 0) {
         for (uint32_t i = 0; i < pl->count; i++)
             sections[i] = 0;
@@ -4446,7 +4261,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *pl,
 extern "C" ZlibReturn zsc_hip_inflate_plan_index_enable(zsc_hip_inflate_plan *pl, I32 enable)
 {
     ZSC_ASSERT(pl != Z_NULL);
-    if (!pl->chunks)
+    if (pl->kind != INF_CHUNKS)
         return Z_STREAM_ERROR;
     pl->cp.keep_index = enable ? 1u : 0u;
     return Z_OK;
@@ -4456,7 +4271,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_index_enable(zsc_hip_inflate_plan *pl
 static ZlibReturn idx_records(zsc_hip_inflate_plan *pl, U32 stream, const std::vector<ZidxRec> **recs,
                               uint64_t *wbytes)
 {
-    if (!pl->chunks || !pl->cp.keep_index || stream >= pl->count || !pl->last_dst)
+    if (pl->kind != INF_CHUNKS || !pl->cp.keep_index || stream >= pl->count || !pl->last_dst)
         return Z_STREAM_ERROR;
     auto hit = pl->idx_recs.find(stream);
     if (hit == pl->idx_recs.end()) {
@@ -4601,9 +4416,90 @@ extern "C" uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_pla
     return pl ? pl->scratch_bytes : 0;
 }
 
+/* host-pointer batch: lay the streams out one behind the other, make the plan (create(&plan, source offsets,
+ * destination offsets)), stage the sources through one device buffer, run, fetch the results, copy the
+ * outputs back (dests; null for a plan that writes nothing) and, of a check plan, the values; tear down */
+template <class Create>
+static ZlibReturn uncompress_batch_host(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
+                                        U32 *dest_lens, I32 *statuses, U32 *check_values, Create create)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(sources != Z_NULL);
+    ZSC_ASSERT(source_lens != Z_NULL);
+    ZSC_ASSERT(dest_lens != Z_NULL);
+    if (count == 0)
+        return Z_OK;
+    if (zsc_hip_init(-1) != Z_OK)
+        return Z_STREAM_ERROR;
+    std::vector<uint64_t> so(count), dof(count);
+    uint64_t sb = 0, db = 0;
+    for (U32 i = 0; i < count; i++) {
+        so[i] = sb;
+        dof[i] = db;
+        sb += ((uint64_t)source_lens[i] + 64u + 15u) & ~15ull;
+        db += ((uint64_t)dest_lens[i] + 64u + 15u) & ~15ull;
+    }
+    zsc_hip_inflate_plan *pl = nullptr;
+    ZlibReturn rc = create(&pl, so.data(), dof.data());
+    if (rc != Z_OK)
+        return rc;
+    DevBuf d_src, d_dst;
+    if (!d_src.ensure(sb + 64) || (dests && !d_dst.ensure(db + 64)))
+        rc = Z_MEM_ERROR;
+    for (U32 i = 0; i < count && rc == Z_OK; i++) {
+        ZSC_ASSERT(sources[i] != Z_NULL);
+        if (source_lens[i] && hipMemcpy((uint8_t *)d_src.p + so[i], sources[i], source_lens[i],
+                                        hipMemcpyHostToDevice) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    std::vector<U32> outl(count), used(count), vals(count);
+    std::vector<I32> stat(count);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_run(pl, d_src.p, d_dst.p, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_results(pl, outl.data(), used.data(), stat.data(), nullptr);
+    if (rc == Z_OK && pl->has_rings())
+        rc = zsc_hip_inflate_plan_check_values(pl, vals.data());
+    for (U32 i = 0; i < count && rc == Z_OK; i++) {
+        if (dests) {
+            ZSC_ASSERT(dests[i] != Z_NULL);
+            if (outl[i] && hipMemcpy(dests[i], (uint8_t *)d_dst.p + dof[i], outl[i],
+                                     hipMemcpyDeviceToHost) != hipSuccess)
+                rc = Z_STREAM_ERROR;
+        }
+        dest_lens[i] = outl[i];
+        source_lens[i] = used[i];
+        if (statuses)
+            statuses[i] = stat[i];
+        if (check_values)
+            check_values[i] = vals[i];
+    }
+    d_src.release();
+    d_dst.release();
+    zsc_hip_inflate_plan_destroy(pl);
+    return rc;
+}
+
+/* the batches that write their outputs: a plain (0), sections (1), chunks (2), resync (3) or indexed (4) plan */
 static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
                                         U32 *dest_lens, I32 *statuses, I32 window_bits, int kind,
-                                        const U8 *const *indexes = Z_NULL, const uint64_t *index_lens = Z_NULL);
+                                        const U8 *const *indexes = Z_NULL, const uint64_t *index_lens = Z_NULL)
+{
+    ZSC_ASSERT(dests != Z_NULL);
+    return uncompress_batch_host(
+        count, sources, source_lens, dests, dest_lens, statuses, Z_NULL,
+        [&](zsc_hip_inflate_plan **pl, const uint64_t *so, const uint64_t *dof) {
+            return kind == 1 ? zsc_hip_inflate_plan_create_sections(pl, count, source_lens, so, dest_lens, dof,
+                                                                    window_bits)
+                   : kind == 2 ? zsc_hip_inflate_plan_create_chunks(pl, count, source_lens, so, dest_lens, dof,
+                                                                    window_bits, 0)
+                   : kind == 3 ? zsc_hip_inflate_plan_create_resync(pl, count, source_lens, so, dest_lens, dof,
+                                                                    window_bits)
+                   : kind == 4 ? zsc_hip_inflate_plan_create_indexed(pl, count, source_lens, so, dest_lens, dof,
+                                                                     window_bits, indexes, index_lens, Z_NULL, Z_NULL)
+                               : zsc_hip_inflate_plan_create(pl, count, source_lens, so, dest_lens, dof, window_bits);
+        });
+}
 
 /* host-pointer batch: stage through one pair of device buffers */
 extern "C" ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources,
@@ -4647,50 +4543,11 @@ extern "C" ZlibReturn zsc_hip_uncompress_indexed_batch(U32 count, const U8 *cons
 extern "C" ZlibReturn zsc_hip_uncompress_sizes_batch(U32 count, const U8 *const *sources, U32 *source_lens,
                                                      U32 *dest_lens, I32 *statuses, I32 window_bits)
 {
-    DeviceScope scope;
-    ZSC_ASSERT(sources != Z_NULL);
-    ZSC_ASSERT(source_lens != Z_NULL);
-    ZSC_ASSERT(dest_lens != Z_NULL);
-    if (count == 0)
-        return Z_OK;
-    if (zsc_hip_init(-1) != Z_OK)
-        return Z_STREAM_ERROR;
-    std::vector<uint64_t> so(count);
-    uint64_t sb = 0;
-    for (U32 i = 0; i < count; i++) {
-        so[i] = sb;
-        sb += ((uint64_t)source_lens[i] + 64u + 15u) & ~15ull;
-    }
-    zsc_hip_inflate_plan *pl = nullptr;
-    ZlibReturn rc = zsc_hip_inflate_plan_create_size(&pl, count, source_lens, so.data(), dest_lens, window_bits, 0);
-    if (rc != Z_OK)
-        return rc;
-    DevBuf d_src;
-    if (!d_src.ensure(sb + 64)) {
-        zsc_hip_inflate_plan_destroy(pl);
-        return Z_MEM_ERROR;
-    }
-    for (U32 i = 0; i < count && rc == Z_OK; i++) {
-        ZSC_ASSERT(sources[i] != Z_NULL);
-        if (source_lens[i] && hipMemcpy((uint8_t *)d_src.p + so[i], sources[i], source_lens[i],
-                                        hipMemcpyHostToDevice) != hipSuccess)
-            rc = Z_STREAM_ERROR;
-    }
-    std::vector<U32> outl(count), used(count);
-    std::vector<I32> stat(count);
-    if (rc == Z_OK)
-        rc = zsc_hip_inflate_plan_run(pl, d_src.p, nullptr, nullptr);
-    if (rc == Z_OK)
-        rc = zsc_hip_inflate_plan_results(pl, outl.data(), used.data(), stat.data(), nullptr);
-    for (U32 i = 0; i < count && rc == Z_OK; i++) {
-        dest_lens[i] = outl[i];
-        source_lens[i] = used[i];
-        if (statuses)
-            statuses[i] = stat[i];
-    }
-    d_src.release();
-    zsc_hip_inflate_plan_destroy(pl);
-    return rc;
+    return uncompress_batch_host(count, sources, source_lens, Z_NULL, dest_lens, statuses, Z_NULL,
+                                 [&](zsc_hip_inflate_plan **pl, const uint64_t *so, const uint64_t *) {
+                                     return zsc_hip_inflate_plan_create_size(pl, count, source_lens, so, dest_lens,
+                                                                             window_bits, 0);
+                                 });
 }
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_check_values(zsc_hip_inflate_plan *pl, U32 *values)
@@ -4698,7 +4555,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_check_values(zsc_hip_inflate_plan *pl
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     ZSC_ASSERT(values != Z_NULL);
-    if (!pl->check || !pl->size_ran)
+    if (!pl->has_rings() || !pl->size_ran)
         return Z_STREAM_ERROR;
     if (pl->count == 0)
         return Z_OK;
@@ -4719,54 +4576,11 @@ extern "C" ZlibReturn zsc_hip_uncompress_check_batch(U32 count, const U8 *const 
                                                      U32 *dest_lens, I32 *statuses, U32 *check_values,
                                                      I32 window_bits)
 {
-    DeviceScope scope;
-    ZSC_ASSERT(sources != Z_NULL);
-    ZSC_ASSERT(source_lens != Z_NULL);
-    ZSC_ASSERT(dest_lens != Z_NULL);
-    if (count == 0)
-        return Z_OK;
-    if (zsc_hip_init(-1) != Z_OK)
-        return Z_STREAM_ERROR;
-    std::vector<uint64_t> so(count);
-    uint64_t sb = 0;
-    for (U32 i = 0; i < count; i++) {
-        so[i] = sb;
-        sb += ((uint64_t)source_lens[i] + 64u + 15u) & ~15ull;
-    }
-    zsc_hip_inflate_plan *pl = nullptr;
-    ZlibReturn rc = zsc_hip_inflate_plan_create_check(&pl, count, source_lens, so.data(), dest_lens, window_bits, 0);
-    if (rc != Z_OK)
-        return rc;
-    DevBuf d_src;
-    if (!d_src.ensure(sb + 64)) {
-        zsc_hip_inflate_plan_destroy(pl);
-        return Z_MEM_ERROR;
-    }
-    for (U32 i = 0; i < count && rc == Z_OK; i++) {
-        ZSC_ASSERT(sources[i] != Z_NULL);
-        if (source_lens[i] && hipMemcpy((uint8_t *)d_src.p + so[i], sources[i], source_lens[i],
-                                        hipMemcpyHostToDevice) != hipSuccess)
-            rc = Z_STREAM_ERROR;
-    }
-    std::vector<U32> outl(count), used(count), vals(count);
-    std::vector<I32> stat(count);
-    if (rc == Z_OK)
-        rc = zsc_hip_inflate_plan_run(pl, d_src.p, nullptr, nullptr);
-    if (rc == Z_OK)
-        rc = zsc_hip_inflate_plan_results(pl, outl.data(), used.data(), stat.data(), nullptr);
-    if (rc == Z_OK)
-        rc = zsc_hip_inflate_plan_check_values(pl, vals.data());
-    for (U32 i = 0; i < count && rc == Z_OK; i++) {
-        dest_lens[i] = outl[i];
-        source_lens[i] = used[i];
-        if (statuses)
-            statuses[i] = stat[i];
-        if (check_values)
-            check_values[i] = vals[i];
-    }
-    d_src.release();
-    zsc_hip_inflate_plan_destroy(pl);
-    return rc;
+    return uncompress_batch_host(count, sources, source_lens, Z_NULL, dest_lens, statuses, check_values,
+                                 [&](zsc_hip_inflate_plan **pl, const uint64_t *so, const uint64_t *) {
+                                     return zsc_hip_inflate_plan_create_check(pl, count, source_lens, so, dest_lens,
+                                                                              window_bits, 0);
+                                 });
 }
 
 /* ---- packing an inflate plan's outputs, unpacking, and the host images (pack.h) ----------------- */
@@ -4775,7 +4589,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_pack_enable(zsc_hip_inflate_plan *pl,
 {
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
-    if (!pack_align_ok(align) || pl->size_only) /* (a size plan has no outputs to pack) */
+    if (!pack_align_ok(align) || pl->writes_nothing()) /* (a size plan has no outputs to pack) */
         return Z_STREAM_ERROR;
     if (pl->pack.on) {
         pack_set_align(pl->pack, align);
@@ -5033,76 +4847,6 @@ extern "C" ZlibReturn zsc_hip_uncompress_batch_packed(U32 count, const U8 *sourc
     (void)hipDeviceSynchronize();
     for (DevBuf *b : {&d_img, &d_src, &d_dst, &d_packed, &d_table, &d_lens, &d_slots})
         b->release();
-    zsc_hip_inflate_plan_destroy(pl);
-    return rc;
-}
-
-static ZlibReturn uncompress_batch_impl(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
-                                        U32 *dest_lens, I32 *statuses, I32 window_bits, int kind,
-                                        const U8 *const *indexes, const uint64_t *index_lens)
-{
-    DeviceScope scope;
-    ZSC_ASSERT(sources != Z_NULL);
-    ZSC_ASSERT(source_lens != Z_NULL);
-    ZSC_ASSERT(dests != Z_NULL);
-    ZSC_ASSERT(dest_lens != Z_NULL);
-    if (count == 0)
-        return Z_OK;
-    if (zsc_hip_init(-1) != Z_OK)
-        return Z_STREAM_ERROR;
-    std::vector<uint64_t> so(count), dof(count);
-    uint64_t sb = 0, db = 0;
-    for (U32 i = 0; i < count; i++) {
-        so[i] = sb;
-        dof[i] = db;
-        sb += ((uint64_t)source_lens[i] + 64u + 15u) & ~15ull;
-        db += ((uint64_t)dest_lens[i] + 64u + 15u) & ~15ull;
-    }
-    zsc_hip_inflate_plan *pl = nullptr;
-    ZlibReturn rc = kind == 1 ? zsc_hip_inflate_plan_create_sections(&pl, count, source_lens, so.data(), dest_lens,
-                                                                     dof.data(), window_bits)
-                    : kind == 2 ? zsc_hip_inflate_plan_create_chunks(&pl, count, source_lens, so.data(), dest_lens,
-                                                                     dof.data(), window_bits, 0)
-                    : kind == 3 ? zsc_hip_inflate_plan_create_resync(&pl, count, source_lens, so.data(), dest_lens,
-                                                                     dof.data(), window_bits)
-                    : kind == 4 ? zsc_hip_inflate_plan_create_indexed(&pl, count, source_lens, so.data(), dest_lens,
-                                                                      dof.data(), window_bits, indexes, index_lens,
-                                                                      Z_NULL, Z_NULL)
-                                : zsc_hip_inflate_plan_create(&pl, count, source_lens, so.data(), dest_lens,
-                                                              dof.data(), window_bits);
-    if (rc != Z_OK)
-        return rc;
-    DevBuf d_src, d_dst;
-    if (!d_src.ensure(sb + 64) || !d_dst.ensure(db + 64)) {
-        d_src.release();
-        d_dst.release();
-        zsc_hip_inflate_plan_destroy(pl);
-        return Z_MEM_ERROR;
-    }
-    for (U32 i = 0; i < count && rc == Z_OK; i++) {
-        ZSC_ASSERT(sources[i] != Z_NULL);
-        if (source_lens[i] && hipMemcpy((uint8_t *)d_src.p + so[i], sources[i], source_lens[i],
-                                        hipMemcpyHostToDevice) != hipSuccess)
-            rc = Z_STREAM_ERROR;
-    }
-    std::vector<U32> outl(count), used(count);
-    std::vector<I32> stat(count);
-    if (rc == Z_OK)
-        rc = zsc_hip_inflate_plan_run(pl, d_src.p, d_dst.p, nullptr);
-    if (rc == Z_OK)
-        rc = zsc_hip_inflate_plan_results(pl, outl.data(), used.data(), stat.data(), nullptr);
-    for (U32 i = 0; i < count && rc == Z_OK; i++) {
-        ZSC_ASSERT(dests[i] != Z_NULL);
-        if (outl[i] && hipMemcpy(dests[i], (uint8_t *)d_dst.p + dof[i], outl[i],
-                                 hipMemcpyDeviceToHost) != hipSuccess)
-            rc = Z_STREAM_ERROR;
-        dest_lens[i] = outl[i];
-        source_lens[i] = used[i];
-        if (statuses)
-            statuses[i] = stat[i];
-    }
-    d_src.release();
-    d_dst.release();
     zsc_hip_inflate_plan_destroy(pl);
     return rc;
 }
