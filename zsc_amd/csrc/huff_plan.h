@@ -8,9 +8,28 @@
  * overflow repair (:477-507), scan_tree/build_bl_tree (:658-806), and the
  * stored / static / dynamic choice (:902-934).
  *
- * The 64 lanes build the symbol histogram with LDS atomics and copy tables;
- * the heap itself is a ~10k step serial algorithm run by lane 0 out of LDS
- * (6 KiB per wave, so 24+ blocks are in flight per CU to hide its latency).
+ * The heap is replayed step for step by lane 0 out of LDS; what has no serial
+ * dependence is done by the 64 lanes: the symbol histogram (LDS atomics), the
+ * heap's initial contents (ballot + prefix count), the bit counts of the block
+ * (wave reduction), gen_codes (:518-549, a ballot per code length) and the
+ * bit-length tree's part of the header.
+ *
+ * A heap entry is one 32-bit word, HP_WORD(freq, depth, node): smaller() (:377) is
+ * one unsigned compare of two words' keys (word >> 10), and a level of pqdownheap
+ * is one load of two neighbouring words.  An internal node's frequency lives only
+ * in its word.  An entry that leaves the heap for the sorted list above heap_top
+ * keeps its node number and swaps its key, dead from then on, for the number of
+ * its parent (known at that moment), so that there is no parent[] array and
+ * gen_bitlen's walk over the list is one dependent load per node.
+ *
+ * The key's fields: a block has at most 2^15 - 1 symbols (lit_bufsize - 1 at
+ * mem_level 9) plus END_BLOCK, and forcing adds at most 2, so every frequency and
+ * every sum is below 2^17.  A node of depth d in a tree built by merging the two
+ * lightest nodes weighs at least Fib(d + 2) (1, 2, 3, 5, ...: the lighter child of
+ * a merge is at least as heavy as the node merged before it), so with a total
+ * below 2^17 no depth exceeds 24: five bits.  The lane emulation asserts both.
+ *
+ * 4.4 KiB of LDS per wave: 32 blocks are in flight per CU, the most it takes.
  * Output: code tables ready for the bit packer, the exact size of the block in
  * bits (opt_len/static_len are exact), and the dynamic block's header bits.
  */
@@ -19,59 +38,70 @@
 
 #include "wave.h"
 #include "zsc_dev.h"
+#ifdef ZSC_WAVE_EMU
+#include <assert.h>
+#define HP_ASSERT(x) assert(x)
+#else
+#define HP_ASSERT(x) ((void)0)
+#endif
+
+/* a hook for the lane emulation's tests: which rare paths a block took (0: a forced node, 1 + kind: the
+ * overflow repair of that tree, 4 + type: the block's type) */
+#ifndef HP_PATH
+#define HP_PATH(id) ((void)0)
+#endif
 
 #define HP_LCODES 286
 #define HP_DCODES 30
 #define HP_BLCODES 19
 #define HP_HEAP (2 * HP_LCODES + 1)
 
-typedef struct {
-    uint32_t freq[HP_HEAP];
-    uint16_t parent[HP_HEAP];
-    uint16_t len[HP_HEAP];
-    uint16_t code[HP_HEAP];
-    int max_code;
-} HpTree;
+#define HP_NODE_MASK 1023u
+#define HP_WORD(freq, depth, node) (((uint32_t)(freq) << 15) | ((uint32_t)(depth) << 10) | (uint32_t)(node))
+#define HP_KEY(w) ((w) >> 10)
+#define HP_FREQ(w) ((w) >> 15)
+#define HP_DEPTH(w) (((w) >> 10) & 31u)
+#define HP_NO_SYM 0xffffffffu /* (no symbol has a distance of 65 535) */
+#ifndef HP_HIST_LOADS
+#define HP_HIST_LOADS 4 /* symbols a lane asks for before it counts the first of them */
+#endif
 
 typedef struct {
-    uint32_t freq[2 * HP_DCODES + 1];
-    uint16_t parent[2 * HP_DCODES + 1];
-    uint16_t len[2 * HP_DCODES + 2];
-    uint16_t code[2 * HP_DCODES + 1];
-    int max_code;
-} HpTreeD;
-
-typedef struct {
-    uint32_t freq[2 * HP_BLCODES + 1];
-    uint16_t parent[2 * HP_BLCODES + 1];
-    uint16_t len[2 * HP_BLCODES + 1];
-    uint16_t code[2 * HP_BLCODES + 1];
-    int max_code;
-} HpTreeB;
-
-typedef struct {
-    HpTree lt;
-    HpTreeD dt;
-    HpTreeB bt;
-    uint16_t heap[HP_HEAP];
-    uint8_t depth[HP_HEAP];
-    uint16_t per_len[16];
-    uint32_t opt_bits, static_bits;
-    int heap_n, heap_top;
-    /* header bit writer */
-    uint8_t hdr[ZD_HDR_BYTES];
-    uint32_t hdr_acc, hdr_fill, hdr_pos;
+    uint32_t heap[HP_HEAP + 1]; /* [1 .. heap_n] the heap, [heap_top .. HP_HEAP) the sorted list; the pair
+                                   (heap[j], heap[j + 1]) of an even j is 8-byte aligned */
+    uint32_t lfreq[HP_LCODES];  /* leaves only */
+    uint32_t dfreq[HP_DCODES];
+    uint32_t bfreq[HP_BLCODES];
+    uint32_t bsend[HP_BLCODES]; /* the bit-length tree's codes as send_tree wants them: code | len << 16 */
+    uint32_t per_len[16];       /* bl_count, only where the overflow repair needs it */
+    /* code lengths: of every node while gen_bitlen runs, of the leaves from then on (each a multiple of four
+     * bytes long: scan_tree and send_tree read them a word at a time, up to three bytes past max_code + 1) */
+    uint8_t llen[HP_HEAP + 3];
+    uint8_t dlen[2 * HP_DCODES + 4];
+    uint8_t blen[2 * HP_BLCODES + 2];
 } HpLds;
 
-/* a view of one of the three trees plus its static description
- * (reference static_tree_desc, src/trees.c:237-252) */
-typedef struct {
-    uint32_t *freq;
-    uint16_t *parent, *len, *code;
-    int *max_code;
-    int elems, max_len, extra_from, has_static, is_dist;
-    int kind; /* 0 lit/len, 1 dist, 2 bit-length */
-} HpView;
+/* one of the three trees plus its static description (reference static_tree_desc, src/trees.c:237-252) */
+template <int KIND> struct HpTree; /* 0 lit/len, 1 dist, 2 bit-length */
+template <> struct HpTree<0> {
+    enum { elems = HP_LCODES, max_len = 15, has_static = 1 };
+};
+template <> struct HpTree<1> {
+    enum { elems = HP_DCODES, max_len = 15, has_static = 1 };
+};
+template <> struct HpTree<2> {
+    enum { elems = HP_BLCODES, max_len = 7, has_static = 0 };
+};
+
+DEV uint32_t *hp_freq(HpLds *h, int kind)
+{
+    return kind == 0 ? h->lfreq : kind == 1 ? h->dfreq : h->bfreq;
+}
+
+DEV uint8_t *hp_len(HpLds *h, int kind)
+{
+    return kind == 0 ? h->llen : kind == 1 ? h->dlen : h->blen;
+}
 
 /* extra bits: reference src/trees.c:87-94, as arithmetic */
 DEV int hp_extra(int kind, int sym)
@@ -138,154 +168,260 @@ DEV uint32_t hp_bitrev(uint32_t v, int bits) /* bi_reverse, reference src/trees.
     return r;
 }
 
-/* smaller(), reference src/trees.c:377-379 */
-DEV int hp_before(const HpView &t, const uint8_t *depth, int a, int b)
+/* pqdownheap, reference src/trees.c:387-414: `v` goes down from place k of a heap of n words */
+DEV void hp_sift(uint32_t *heap, int n, int k, uint32_t v)
 {
-    return t.freq[a] < t.freq[b] || (t.freq[a] == t.freq[b] && depth[a] <= depth[b]);
-}
-
-/* pqdownheap, reference src/trees.c:387-414 */
-DEV void hp_sift(HpLds *h, const HpView &t, int k)
-{
-    int v = h->heap[k];
-    for (int j = k << 1; j <= h->heap_n; j <<= 1) {
-        if (j < h->heap_n && hp_before(t, h->depth, h->heap[j + 1], h->heap[j]))
+    for (int j = k << 1; j <= n; j <<= 1) {
+        uint32_t c = heap[j];
+        const uint32_t c1 = heap[j + 1]; /* (one load with heap[j]; past the heap's end where j == n, and unused) */
+        if (j < n && HP_KEY(c1) <= HP_KEY(c)) {
+            c = c1;
             j++;
-        if (hp_before(t, h->depth, v, h->heap[j]))
+        }
+        if (HP_KEY(v) <= HP_KEY(c))
             break;
-        h->heap[k] = h->heap[j];
+        heap[k] = c;
         k = j;
     }
-    h->heap[k] = (uint16_t)v;
+    heap[k] = v;
 }
 
-/* build_tree + gen_bitlen + gen_codes, reference src/trees.c:426-652 (serial, lane 0) */
-DEV void hp_build(HpLds *h, const HpView &t)
+/* build_tree's heap and gen_bitlen, reference src/trees.c:445-508 and :612-645: serial, lane 0 only.
+ * `n` words are in the heap, `top` is max_code.  Leaves every node's length in len[]. */
+template <int KIND>
+DEV void hp_heap_and_lengths(HpLds *h, int n, int top)
 {
-    int top = -1;
-    h->heap_n = 0;
-    h->heap_top = HP_HEAP;
-    for (int n = 0; n < t.elems; n++) {
-        if (t.freq[n]) {
-            h->heap[++h->heap_n] = (uint16_t)(top = n);
-            h->depth[n] = 0;
-        } else {
-            t.len[n] = 0;
-        }
-    }
-    while (h->heap_n < 2) { /* :595-610 */
-        int node = top < 2 ? ++top : 0;
-        h->heap[++h->heap_n] = (uint16_t)node;
-        t.freq[node] = 1;
-        h->depth[node] = 0;
-        h->opt_bits--;
-        if (t.has_static)
-            h->static_bits -= t.is_dist ? 5u : hp_static_llen((uint32_t)node);
-    }
-    *t.max_code = top;
-    for (int n = h->heap_n / 2; n >= 1; n--)
-        hp_sift(h, t, n);
+    typedef HpTree<KIND> T;
+    uint32_t *heap = h->heap;
+    uint8_t *len = hp_len(h, KIND);
+    for (int k = n / 2; k >= 1; k--)
+        hp_sift(heap, n, k, heap[k]);
 
-    int node = t.elems;
+    int node = T::elems, ht = HP_HEAP;
     do { /* :624-640 */
-        int a = h->heap[1];
-        h->heap[1] = h->heap[h->heap_n--];
-        hp_sift(h, t, 1);
-        int b = h->heap[1];
-        h->heap[--h->heap_top] = (uint16_t)a;
-        h->heap[--h->heap_top] = (uint16_t)b;
-        t.freq[node] = t.freq[a] + t.freq[b];
-        h->depth[node] = (uint8_t)((h->depth[a] >= h->depth[b] ? h->depth[a] : h->depth[b]) + 1);
-        t.parent[a] = t.parent[b] = (uint16_t)node;
-        h->heap[1] = (uint16_t)node++;
-        hp_sift(h, t, 1);
-    } while (h->heap_n >= 2);
-    h->heap[--h->heap_top] = h->heap[1];
+        const uint32_t a = heap[1];
+        const uint32_t last = heap[n];
+        n--;
+        hp_sift(heap, n, 1, last);
+        const uint32_t b = heap[1];
+        heap[--ht] = ((uint32_t)node << 10) | (a & HP_NODE_MASK);
+        heap[--ht] = ((uint32_t)node << 10) | (b & HP_NODE_MASK);
+        const uint32_t da = HP_DEPTH(a), db = HP_DEPTH(b);
+        const uint32_t depth = (da >= db ? da : db) + 1u, freq = HP_FREQ(a) + HP_FREQ(b);
+        HP_ASSERT(depth < 32u && freq < (1u << 17));
+        hp_sift(heap, n, 1, HP_WORD(freq, depth, node));
+        node++;
+    } while (n >= 2);
+    const int root = (int)(heap[1] & HP_NODE_MASK);
 
-    /* gen_bitlen, :445-508 */
+    /* gen_bitlen, :445-472 (the counts of the block's bits are taken from the final lengths, by all lanes) */
     int over = 0;
-    for (int b = 0; b < 16; b++)
-        h->per_len[b] = 0;
-    t.len[h->heap[h->heap_top]] = 0;
-    int i;
-    for (i = h->heap_top + 1; i < HP_HEAP; i++) {
-        int n = h->heap[i];
-        int bits = t.len[t.parent[n]] + 1;
-        if (bits > t.max_len) {
-            bits = t.max_len;
+    len[root] = 0;
+    uint32_t w = heap[ht];
+    for (int i = ht; i < HP_HEAP; i++) {
+        const uint32_t wn = heap[i + 1]; /* (asked for one node ahead; heap[HP_HEAP] is there and unused) */
+        int bits = len[w >> 10] + 1;
+        if (bits > (int)T::max_len) {
+            bits = T::max_len;
             over++; /* internal nodes count too: :457 runs before :461 */
         }
-        t.len[n] = (uint16_t)bits;
-        if (n > top)
-            continue;
-        h->per_len[bits]++;
-        int xb = n >= t.extra_from ? hp_extra(t.kind, n) : 0;
-        h->opt_bits += t.freq[n] * (uint32_t)(bits + xb);
-        if (t.has_static)
-            h->static_bits += t.freq[n] * ((t.is_dist ? 5u : hp_static_llen((uint32_t)n)) + (uint32_t)xb);
+        len[w & HP_NODE_MASK] = (uint8_t)bits;
+        w = wn;
     }
     if (over > 0) {
+        HP_PATH(1 + KIND);
+        uint32_t *per_len = h->per_len;
+        for (int b = 0; b < 16; b++)
+            per_len[b] = 0;
+        for (int i = ht; i < HP_HEAP; i++) {
+            const int m = (int)(heap[i] & HP_NODE_MASK);
+            if (m <= top)
+                per_len[len[m]]++;
+        }
         do { /* :477-489 */
-            int bits = t.max_len - 1;
-            while (h->per_len[bits] == 0)
+            int bits = T::max_len - 1;
+            while (per_len[bits] == 0)
                 bits--;
-            h->per_len[bits]--;
-            h->per_len[bits + 1] += 2;
-            h->per_len[t.max_len]--;
+            per_len[bits]--;
+            per_len[bits + 1] += 2;
+            per_len[T::max_len]--;
             over -= 2;
         } while (over > 0);
-        for (int bits = t.max_len; bits != 0; bits--) { /* :496-507 */
-            int n = h->per_len[bits];
-            while (n != 0) {
-                int m = h->heap[--i];
+        int i = HP_HEAP;
+        for (int bits = T::max_len; bits != 0; bits--) { /* :496-507 */
+            uint32_t k = per_len[bits];
+            while (k != 0) {
+                const int m = (int)(heap[--i] & HP_NODE_MASK);
                 if (m > top)
                     continue;
-                if (t.len[m] != (uint16_t)bits) {
-                    h->opt_bits += ((uint32_t)bits - t.len[m]) * t.freq[m];
-                    t.len[m] = (uint16_t)bits;
-                }
-                n--;
+                len[m] = (uint8_t)bits;
+                k--;
             }
         }
     }
-    /* gen_codes, :518-549 */
-    uint16_t next[16];
-    uint32_t code = 0;
-    for (int b = 1; b <= 15; b++) {
-        code = (code + h->per_len[b - 1]) << 1;
-        next[b] = (uint16_t)code;
+}
+
+/* build_tree + gen_bitlen + gen_codes of one tree, reference src/trees.c:426-652; called by the whole wave.
+ * Adds the tree's part to opt_bits / static_bits (wave-uniform) and returns max_code.  The lit/len and distance
+ * trees' codes go straight to the plan, the bit-length tree's to h->bsend. */
+template <int KIND>
+DEV int hp_build(HpLds *h, ZdBlockPlan *plan, uint32_t &opt_bits, uint32_t &static_bits)
+{
+    typedef HpTree<KIND> T;
+    enum { NCH = (T::elems + WAVE - 1) / WAVE };
+    uint32_t *const freq = hp_freq(h, KIND);
+    uint8_t *const len = hp_len(h, KIND);
+    int top = -1, n = 0;
+    /* the symbols in use, in rising order, are the heap's first contents (:583-590) */
+    for (int c = 0; c < NCH; c++) {
+        LANEVAR(uint32_t, f);
+        FOR_LANES
+        {
+            const int s = c * WAVE + LANE;
+            LV(f) = s < (int)T::elems ? freq[s] : 0u;
+            if (s < (int)T::elems)
+                len[s] = 0;
+        }
+        const uint64_t m = BALLOT(f);
+        FOR_LANES
+        {
+            if (LV(f))
+                h->heap[n + 1 + POPC64(m & ((1ull << LANE) - 1ull))] = HP_WORD(LV(f), 0, c * WAVE + LANE);
+        }
+        if (m) {
+            n += POPC64(m);
+            top = c * WAVE + 63 - CLZ64(m);
+        }
     }
-    for (int n = 0; n <= top; n++) {
-        int l = t.len[n];
-        if (l)
-            t.code[n] = (uint16_t)hp_bitrev(next[l]++, l);
+    while (n < 2) { /* :595-610 */
+        HP_PATH(0);
+        const int node = top < 2 ? ++top : 0;
+        n++;
+        ON_LANE0
+        {
+            h->heap[n] = HP_WORD(1, 0, node);
+            freq[node] = 1;
+        }
+        opt_bits--;
+        if (T::has_static)
+            static_bits -= KIND == 1 ? 5u : hp_static_llen((uint32_t)node);
     }
+    WAVE_SYNC();
+    ON_LANE0
+    {
+        hp_heap_and_lengths<KIND>(h, n, top);
+    }
+    WAVE_SYNC();
+
+    /* the block's bits under this tree and under the static one (:461-471 and :501-505, summed up from the
+     * final lengths: the low word counts the dynamic bits, the high word the static ones, each far below 2^32) */
+    LANEARR(uint32_t, ln, NCH);
+    LANEARR(uint32_t, cd, NCH);
+    LANEVAR(uint64_t, bits);
+    FOR_LANES
+    {
+        LV(bits) = 0;
+    }
+    UNROLL_FULL
+    for (int c = 0; c < NCH; c++) {
+        FOR_LANES
+        {
+            const int s = c * WAVE + LANE;
+            uint32_t l = 0;
+            if (s < (int)T::elems) {
+                l = len[s];
+                const uint32_t fr = freq[s], xb = (uint32_t)hp_extra(KIND, s);
+                LV(bits) += (uint64_t)(fr * (l + xb));
+                if (T::has_static)
+                    LV(bits) += (uint64_t)(fr * ((KIND == 1 ? 5u : hp_static_llen((uint32_t)s)) + xb)) << 32;
+            }
+            LVA(ln, c) = l;
+            LVA(cd, c) = 0;
+        }
+    }
+    const uint64_t total = WAVE_SUM(bits);
+    opt_bits += (uint32_t)total;
+    static_bits += (uint32_t)(total >> 32);
+
+    /* gen_codes, :518-549: the symbols of one length get consecutive codes in rising order, so a symbol's code
+     * is its length's first one plus the number of lower symbols of that length */
+    uint32_t code = 0, count = 0;
+    for (int l = 1; l <= (int)T::max_len; l++) {
+        code = (code + count) << 1;
+        uint32_t run = code;
+        UNROLL_FULL
+        for (int c = 0; c < NCH; c++) {
+            LANEVAR(uint32_t, is);
+            FOR_LANES
+            {
+                LV(is) = LVA(ln, c) == (uint32_t)l;
+            }
+            const uint64_t m = BALLOT(is);
+            FOR_LANES
+            {
+                if (LV(is))
+                    LVA(cd, c) = run + (uint32_t)POPC64(m & ((1ull << LANE) - 1ull));
+            }
+            run += (uint32_t)POPC64(m);
+        }
+        count = run - code;
+    }
+    UNROLL_FULL
+    for (int c = 0; c < NCH; c++) {
+        FOR_LANES
+        {
+            const int s = c * WAVE + LANE;
+            if (s < (int)T::elems) {
+                const uint32_t l = LVA(ln, c);
+                const uint32_t rev = l ? BREV32(LVA(cd, c)) >> (32u - l) : 0u; /* bi_reverse */
+                if (KIND == 0) {
+                    plan->lcode[s] = (uint16_t)rev;
+                    plan->llen[s] = (uint8_t)l;
+                } else if (KIND == 1) {
+                    plan->dcode[s] = (uint16_t)rev;
+                    plan->dlen[s] = (uint8_t)l;
+                } else {
+                    h->bsend[s] = rev | (l << 16);
+                }
+            }
+        }
+    }
+    return top;
+}
+
+/* the code length of symbol i, through a word that holds four of them */
+DEV uint32_t hp_len_at(const uint8_t *len, uint32_t &word, int i)
+{
+    if ((i & 3) == 0)
+        __builtin_memcpy(&word, __builtin_assume_aligned(len + i, 4), 4);
+    return (word >> ((i & 3) * 8)) & 0xffu;
 }
 
 /* scan_tree, reference src/trees.c:658-707 */
-DEV void hp_scan(HpLds *h, uint16_t *len, int max_code)
+DEV void hp_scan(HpLds *h, uint8_t *len, int max_code)
 {
-    int prev = -1, next = len[0], count = 0, hi = 7, lo = 4;
+    len[max_code + 1] = 0xff; /* guard, :674 */
+    uint32_t word = 0;
+    int prev = -1, next = (int)hp_len_at(len, word, 0), count = 0, hi = 7, lo = 4;
     if (next == 0) {
         hi = 138;
         lo = 3;
     }
-    len[max_code + 1] = 0xffff; /* guard, :674 */
     for (int n = 0; n <= max_code; n++) {
         int cur = next;
-        next = len[n + 1];
+        next = (int)hp_len_at(len, word, n + 1);
         if (++count < hi && cur == next)
             continue;
         if (count < lo)
-            h->bt.freq[cur] += (uint32_t)count;
+            LDS_ADD_U32(&h->bfreq[cur], (uint32_t)count);
         else if (cur != 0) {
             if (cur != prev)
-                h->bt.freq[cur]++;
-            h->bt.freq[16]++;
+                LDS_ADD_U32(&h->bfreq[cur], 1u);
+            LDS_ADD_U32(&h->bfreq[16], 1u);
         } else if (count <= 10)
-            h->bt.freq[17]++;
+            LDS_ADD_U32(&h->bfreq[17], 1u);
         else
-            h->bt.freq[18]++;
+            LDS_ADD_U32(&h->bfreq[18], 1u);
         count = 0;
         prev = cur;
         if (next == 0) {
@@ -301,48 +437,60 @@ DEV void hp_scan(HpLds *h, uint16_t *len, int max_code)
     }
 }
 
-/* header bit writer (send_bits into the LDS staging copy of the block header) */
-DEV void hp_put(HpLds *h, uint32_t value, int nbits)
+/* header bit writer (send_bits into the plan's copy of the block header): the bits gather in a register
+ * pair and leave as whole 32-bit words */
+typedef struct {
+    uint64_t acc;
+    uint32_t fill, pos; /* bits in acc (below 32 between calls), bytes stored */
+    uint8_t *out;       /* 4-byte aligned */
+} HpBits;
+
+DEV void hp_put(HpBits &w, uint32_t value, int nbits) /* nbits <= 32 */
 {
-    h->hdr_acc |= value << h->hdr_fill;
-    h->hdr_fill += (uint32_t)nbits;
-    while (h->hdr_fill >= 8) {
-        h->hdr[h->hdr_pos++] = (uint8_t)h->hdr_acc;
-        h->hdr_acc >>= 8;
-        h->hdr_fill -= 8;
+    w.acc |= (uint64_t)value << w.fill;
+    w.fill += (uint32_t)nbits;
+    if (w.fill >= 32) {
+        const uint32_t lo = (uint32_t)w.acc;
+        __builtin_memcpy(__builtin_assume_aligned(w.out + w.pos, 4), &lo, 4);
+        w.pos += 4;
+        w.acc >>= 32;
+        w.fill -= 32;
     }
 }
 
-/* send_tree, reference src/trees.c:713-773 */
-DEV void hp_send_lengths(HpLds *h, const uint16_t *len, int max_code)
+/* send_tree, reference src/trees.c:713-773 (len[max_code + 1] still holds scan_tree's guard) */
+DEV void hp_send_lengths(HpLds *h, HpBits &w, const uint8_t *len, int max_code)
 {
-    int prev = -1, next = len[0], count = 0, hi = 7, lo = 4;
+    uint32_t word = 0;
+    int prev = -1, next = (int)hp_len_at(len, word, 0), count = 0, hi = 7, lo = 4;
     if (next == 0) {
         hi = 138;
         lo = 3;
     }
     for (int n = 0; n <= max_code; n++) {
         int cur = next;
-        next = len[n + 1];
+        next = (int)hp_len_at(len, word, n + 1);
         if (++count < hi && cur == next)
             continue;
         if (count < lo) {
+            const uint32_t s = h->bsend[cur];
             do
-                hp_put(h, h->bt.code[cur], h->bt.len[cur]);
+                hp_put(w, s & 0xffffu, (int)(s >> 16));
             while (--count != 0);
         } else if (cur != 0) {
             if (cur != prev) {
-                hp_put(h, h->bt.code[cur], h->bt.len[cur]);
+                const uint32_t s = h->bsend[cur];
+                hp_put(w, s & 0xffffu, (int)(s >> 16));
                 count--;
             }
-            hp_put(h, h->bt.code[16], h->bt.len[16]);
-            hp_put(h, (uint32_t)(count - 3), 2);
+            const uint32_t s = h->bsend[16];
+            hp_put(w, (s & 0xffffu) | ((uint32_t)(count - 3) << (s >> 16)), (int)(s >> 16) + 2);
         } else if (count <= 10) {
-            hp_put(h, h->bt.code[17], h->bt.len[17]);
-            hp_put(h, (uint32_t)(count - 3), 3);
+            const uint32_t s = h->bsend[17];
+            hp_put(w, (s & 0xffffu) | ((uint32_t)(count - 3) << (s >> 16)), (int)(s >> 16) + 3);
         } else {
-            hp_put(h, h->bt.code[18], h->bt.len[18]);
-            hp_put(h, (uint32_t)(count - 11), 7);
+            const uint32_t s = h->bsend[18];
+            hp_put(w, (s & 0xffffu) | ((uint32_t)(count - 11) << (s >> 16)), (int)(s >> 16) + 7);
         }
         count = 0;
         prev = cur;
@@ -357,6 +505,15 @@ DEV void hp_send_lengths(HpLds *h, const uint16_t *len, int max_code)
             lo = 4;
         }
     }
+}
+
+/* bl_order, reference src/trees.c:96-99: five bits a symbol, twelve symbols in the first word */
+DEV uint32_t hp_bl_order(int r)
+{
+    const uint64_t a = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 |
+                       6ull << 35 | 10ull << 40 | 5ull << 45 | 11ull << 50 | 4ull << 55;
+    const uint64_t b = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
+    return (uint32_t)((r < 12 ? a >> (5 * r) : b >> (5 * (r - 12))) & 31u);
 }
 
 /* plan one block: `syms` points at the block's first symbol */
@@ -365,121 +522,119 @@ DEV void huff_plan_block(const uint32_t *syms, const ZdBlockRec *rec, uint32_t s
 {
     const uint32_t count = rec->sym_count;
     /* init_block, reference src/trees.c:336-356 */
-    for (int i = 0; i < HP_HEAP; i += WAVE) {
+    for (int i = 0; i < HP_LCODES; i += WAVE) {
         FOR_LANES
         {
-            if (i + LANE < HP_HEAP)
-                h->lt.freq[i + LANE] = 0;
+            if (i + LANE < HP_LCODES)
+                h->lfreq[i + LANE] = i + LANE == 256 ? 1u : 0u; /* (END_BLOCK) */
         }
     }
-    FOR_LANES
-    {
-        if (LANE < 2 * HP_DCODES + 1)
-            h->dt.freq[LANE] = 0;
-        if (LANE < 2 * HP_BLCODES + 1)
-            h->bt.freq[LANE] = 0;
-    }
-    /* symbol statistics, reference include/zsc/deflate.h:338-354 */
-    for (uint32_t s = 0; s < count; s += WAVE) {
+    for (int i = 0; i < HP_DCODES; i += WAVE) {
         FOR_LANES
         {
-            uint32_t i = s + (uint32_t)LANE;
-            if (i < count) {
-                uint32_t v = syms[i];
-                uint32_t dist = v >> 16, lc = v & 0xff;
-                if (dist == 0) {
-                    LDS_ADD_U32(&h->lt.freq[lc], 1u);
+            if (i + LANE < HP_DCODES)
+                h->dfreq[i + LANE] = 0;
+            if (i + LANE < HP_BLCODES)
+                h->bfreq[i + LANE] = 0;
+        }
+    }
+    WAVE_SYNC();
+    /* symbol statistics, reference include/zsc/deflate.h:338-354; HP_HIST_LOADS loads in flight per lane */
+    for (uint32_t s = 0; s < count; s += HP_HIST_LOADS * WAVE) {
+        FOR_LANES
+        {
+            uint32_t v[HP_HIST_LOADS];
+            UNROLL_FULL
+            for (int k = 0; k < HP_HIST_LOADS; k++) {
+                const uint32_t i = s + (uint32_t)(k * WAVE + LANE);
+                v[k] = i < count ? syms[i] : HP_NO_SYM;
+            }
+            UNROLL_FULL
+            for (int k = 0; k < HP_HIST_LOADS; k++) {
+                const uint32_t dist = v[k] >> 16, lc = v[k] & 0xff;
+                if (v[k] == HP_NO_SYM) {
+                } else if (dist == 0) {
+                    LDS_ADD_U32(&h->lfreq[lc], 1u);
                 } else {
-                    LDS_ADD_U32(&h->lt.freq[257 + hp_len_code(lc)], 1u);
-                    LDS_ADD_U32(&h->dt.freq[hp_dist_code(dist - 1)], 1u);
+                    LDS_ADD_U32(&h->lfreq[257 + hp_len_code(lc)], 1u);
+                    LDS_ADD_U32(&h->dfreq[hp_dist_code(dist - 1)], 1u);
                 }
             }
         }
     }
     WAVE_SYNC();
-    int last_bl = 0;
-    uint32_t type = ZD_BT_DYNAMIC;
+    uint32_t opt_bits = 0, static_bits = 0;
+    const int lmax = hp_build<0>(h, plan, opt_bits, static_bits);
+    const int dmax = hp_build<1>(h, plan, opt_bits, static_bits);
+    /* build_bl_tree, reference src/trees.c:779-806 */
     ON_LANE0
     {
-        h->lt.freq[256] = 1; /* END_BLOCK */
-        h->opt_bits = h->static_bits = 0;
-        HpView vl = {h->lt.freq, h->lt.parent, h->lt.len, h->lt.code, &h->lt.max_code,
-                     HP_LCODES, 15, 257, 1, 0, 0};
-        HpView vd = {h->dt.freq, h->dt.parent, h->dt.len, h->dt.code, &h->dt.max_code,
-                     HP_DCODES, 15, 0, 1, 1, 1};
-        HpView vb = {h->bt.freq, h->bt.parent, h->bt.len, h->bt.code, &h->bt.max_code,
-                     HP_BLCODES, 7, 0, 0, 0, 2};
-        hp_build(h, vl);
-        hp_build(h, vd);
-        /* build_bl_tree, reference src/trees.c:779-806 */
-        hp_scan(h, h->lt.len, h->lt.max_code);
-        hp_scan(h, h->dt.len, h->dt.max_code);
-        hp_build(h, vb);
-        const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        for (last_bl = HP_BLCODES - 1; last_bl >= 3; last_bl--)
-            if (h->bt.len[order[last_bl]] != 0)
-                break;
-        h->opt_bits += 3u * ((uint32_t)last_bl + 1u) + 5u + 5u + 4u;
-
-        /* reference src/trees.c:902-934 */
-        uint32_t opt_bytes = (h->opt_bits + 3 + 7) >> 3;
-        const uint32_t static_bytes = (h->static_bits + 3 + 7) >> 3;
-        if (static_bytes <= opt_bytes)
-            opt_bytes = static_bytes;
-        if (rec->in_len + 4 <= opt_bytes && rec->stored_ok)
-            type = ZD_BT_STORED;
-        else if (strategy == 4 || static_bytes == opt_bytes)
-            type = ZD_BT_STATIC;
-        else
-            type = ZD_BT_DYNAMIC;
-
-        h->hdr_acc = h->hdr_fill = h->hdr_pos = 0;
-        if (type == ZD_BT_DYNAMIC) {
-            /* send_all_trees, reference src/trees.c:813-833 */
-            hp_put(h, (uint32_t)(h->lt.max_code + 1 - 257), 5);
-            hp_put(h, (uint32_t)(h->dt.max_code + 1 - 1), 5);
-            hp_put(h, (uint32_t)(last_bl + 1 - 4), 4);
-            for (int r = 0; r <= last_bl; r++)
-                hp_put(h, h->bt.len[order[r]], 3);
-            hp_send_lengths(h, h->lt.len, h->lt.max_code);
-            hp_send_lengths(h, h->dt.len, h->dt.max_code);
-        }
-        plan->type = type;
-        plan->hdr_bits = h->hdr_pos * 8 + h->hdr_fill;
-        if (h->hdr_fill)
-            h->hdr[h->hdr_pos] = (uint8_t)h->hdr_acc;
-        plan->body_bits = type == ZD_BT_DYNAMIC ? 3u + h->opt_bits
-                          : type == ZD_BT_STATIC ? 3u + h->static_bits : 0u;
-        plan->bit_off = 0;
+        hp_scan(h, h->llen, lmax);
+        hp_scan(h, h->dlen, dmax);
     }
     WAVE_SYNC();
-    /* publish the tables the bit packer needs */
-    for (int i = 0; i < HP_LCODES; i += WAVE) {
+    hp_build<2>(h, plan, opt_bits, static_bits);
+    WAVE_SYNC();
+    /* the last bit-length code in use in bl_order, and the lengths up to it, three bits each */
+    int last_bl = 0;
+    uint64_t bl_bits = 0;
+    for (int i = 0; i < HP_BLCODES; i += WAVE) {
+        LANEVAR(uint32_t, bl);
         FOR_LANES
         {
-            int s = i + LANE;
-            if (s < HP_LCODES) {
-                int used = s <= h->lt.max_code && h->lt.len[s] != 0;
-                plan->lcode[s] = used ? h->lt.code[s] : (uint16_t)0;
-                plan->llen[s] = used ? (uint8_t)h->lt.len[s] : (uint8_t)0;
-            }
+            LV(bl) = i + LANE < HP_BLCODES ? h->bsend[hp_bl_order(i + LANE)] >> 16 : 0u;
         }
+        const uint64_t m = BALLOT(bl);
+        if (m)
+            last_bl = i + 63 - CLZ64(m);
+        LANEVAR(uint64_t, part);
+        FOR_LANES
+        {
+            LV(part) = i + LANE < HP_BLCODES ? (uint64_t)LV(bl) << (3 * (i + LANE)) : 0ull;
+        }
+        bl_bits += WAVE_SUM(part);
     }
-    FOR_LANES
+    if (last_bl < 3)
+        last_bl = 3;
+    opt_bits += 3u * ((uint32_t)last_bl + 1u) + 5u + 5u + 4u;
+
+    /* reference src/trees.c:902-934 */
+    uint32_t opt_bytes = (opt_bits + 3 + 7) >> 3;
+    const uint32_t static_bytes = (static_bits + 3 + 7) >> 3;
+    if (static_bytes <= opt_bytes)
+        opt_bytes = static_bytes;
+    uint32_t type;
+    if (rec->in_len + 4 <= opt_bytes && rec->stored_ok)
+        type = ZD_BT_STORED;
+    else if (strategy == 4 || static_bytes == opt_bytes)
+        type = ZD_BT_STATIC;
+    else
+        type = ZD_BT_DYNAMIC;
+    ON_LANE0
     {
-        if (LANE < HP_DCODES) {
-            int used = LANE <= h->dt.max_code && h->dt.len[LANE] != 0;
-            plan->dcode[LANE] = used ? h->dt.code[LANE] : (uint16_t)0;
-            plan->dlen[LANE] = used ? (uint8_t)h->dt.len[LANE] : (uint8_t)0;
+        HP_PATH(4 + type);
+        HpBits w = {0, 0, 0, plan->hdr};
+        if (type == ZD_BT_DYNAMIC) {
+            /* send_all_trees, reference src/trees.c:813-833 */
+            hp_put(w, (uint32_t)(lmax + 1 - 257) | (uint32_t)(dmax + 1 - 1) << 5 | (uint32_t)(last_bl + 1 - 4) << 10, 14);
+            const int nb = 3 * (last_bl + 1);
+            const uint64_t sent = nb < 64 ? bl_bits & ((1ull << nb) - 1ull) : bl_bits;
+            hp_put(w, (uint32_t)sent, nb < 32 ? nb : 32);
+            if (nb > 32)
+                hp_put(w, (uint32_t)(sent >> 32), nb - 32);
+            hp_send_lengths(h, w, h->llen, lmax);
+            hp_send_lengths(h, w, h->dlen, dmax);
         }
-    }
-    for (int i = 0; i < (int)ZD_HDR_BYTES; i += WAVE) {
-        FOR_LANES
-        {
-            if (i + LANE < (int)ZD_HDR_BYTES)
-                plan->hdr[i + LANE] = h->hdr[i + LANE];
+        plan->type = type;
+        plan->hdr_bits = w.pos * 8 + w.fill;
+        if (w.fill) {
+            const uint32_t lo = (uint32_t)w.acc;
+            __builtin_memcpy(__builtin_assume_aligned(w.out + w.pos, 4), &lo, 4);
         }
+        plan->body_bits = type == ZD_BT_DYNAMIC ? 3u + opt_bits : type == ZD_BT_STATIC ? 3u + static_bits : 0u;
+        plan->bit_off = 0;
     }
+    WAVE_SYNC(); /* (the next block of this wave's slot reuses the LDS image) */
 }
 
 #endif
