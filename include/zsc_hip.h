@@ -73,6 +73,10 @@ ZlibReturn zsc_hip_compress_sections_batch(U32 count, const U8 *const *sources,
                                            I32 level, I32 window_bits, I32 mem_level,
                                            ZlibStrategy strategy, U32 gzip_header_len);
 
+/* the last zsc_hip_compress_sections_* call of this process: how many sub-batches of its rounds' plans ran
+ * the segmented parser in the wide and in the narrow LDS geometry (runs with joints are always wide) */
+void zsc_hip_compress_sections_last_rings(U32 *wide, U32 *narrow);
+
 /* The same with the streams in device memory: stream i is source_lens[i] bytes at d_input +
  * in_offsets[i] (16-byte aligned) and its compressed stream goes to d_output + out_offsets[i],
  * of which out_caps[i] bytes may be used (the capacity is part of the result: the wrapper hands
@@ -144,6 +148,14 @@ U32 zsc_hip_deflate_plan_sub_batches(const zsc_hip_deflate_plan *plan);
 /* how the plan's long buffers without joints are parsed at levels 4-9: 0 the segmented parser is not
  * used, 1 in super-steps, 2 as a pipeline of segments (the default); fixed when the plan is created */
 I32 zsc_hip_deflate_plan_seg_schedule(const zsc_hip_deflate_plan *plan);
+
+/* the LDS geometry that parser runs in: 0 the segmented parser is not used, 1 the wide ring (the
+ * super-steps' geometry, three workgroups on a CU), 2 the narrow ring of the pipeline alone (four), 3 some
+ * sub-batches the one and some the other.  In plans the narrow ring is built for -- no joints, the
+ * pipeline schedule, window_bits 15, mem_level 8, no match table -- each sub-batch takes it when it has more
+ * long buffers than three per CU; ZSC_HIP_SEG_RING=narrow or =wide, set while the plan is created, says it
+ * for all of them.  Fixed when the plan is created */
+I32 zsc_hip_deflate_plan_seg_ring(const zsc_hip_deflate_plan *plan);
 
 void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *plan);
 

@@ -37,7 +37,7 @@ from .api import (  # noqa: F401
     compress_get_min_work_buf_size, compress_get_max_output_size, compress_get_max_output_size2,
     uncompress_get_min_work_buf_size,
     compress, compress2, compress_gzip, uncompress, uncompress2, uncompress_gzip,
-    compress_batch, compress_sections_batch, compress_sections_device, uncompress_batch, uncompress_sections_batch,
+    compress_batch, compress_sections_batch, compress_sections_device, compress_sections_last_rings, uncompress_batch, uncompress_sections_batch,
     uncompress_chunks_batch, uncompress_resync_batch, DeflatePlan, InflatePlan,
     uncompress_sizes_batch, uncompress_batch_auto, NO_LIMIT, uncompress_check_batch,
     uncompress_indexed_batch, build_indexes, index_info, index_range, compress_batch_indexed,

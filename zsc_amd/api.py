@@ -146,6 +146,10 @@ def _load() -> C.CDLL:
     L.zsc_hip_deflate_plan_sub_batches.restype = C.c_uint32
     L.zsc_hip_deflate_plan_seg_schedule.argtypes = [C.c_void_p]
     L.zsc_hip_deflate_plan_seg_schedule.restype = C.c_int32
+    L.zsc_hip_deflate_plan_seg_ring.argtypes = [C.c_void_p]
+    L.zsc_hip_deflate_plan_seg_ring.restype = C.c_int32
+    L.zsc_hip_compress_sections_last_rings.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.zsc_hip_compress_sections_last_rings.restype = None
     L.zsc_hip_deflate_plan_destroy.argtypes = [C.c_void_p]
     L.zsc_hip_deflate_plan_destroy.restype = None
     L.zsc_hip_deflate_plan_index_enable.argtypes = [C.c_void_p, C.c_uint32]
@@ -360,6 +364,13 @@ def compress_sections_batch(sources: Sequence[bytes], max_block_lens: Sequence[i
                                              window_bits, mem_level, strategy, 0)
     outs = [bufs[i].raw[:dlen[i]] for i in range(count)] if rc == Z_OK else []
     return rc, outs, list(stat)
+
+
+def compress_sections_last_rings() -> Tuple[int, int]:
+    """(wide, narrow): sub-batches of the last compress_sections_* call by the LDS geometry of their parser."""
+    w, n = C.c_uint32(), C.c_uint32()
+    lib.zsc_hip_compress_sections_last_rings(C.byref(w), C.byref(n))
+    return w.value, n.value
 
 
 def compress_sections_device(d_input: int, in_offsets: Sequence[int], source_lens: Sequence[int],
@@ -923,6 +934,12 @@ class DeflatePlan(_Packing):
     def seg_schedule(self) -> str:
         """How long plain buffers are parsed at levels 4-9: "none", "super-steps" or "pipeline"."""
         return ("none", "super-steps", "pipeline")[lib.zsc_hip_deflate_plan_seg_schedule(self._h)]
+
+    @property
+    def seg_ring(self) -> str:
+        """The LDS geometry that parser runs in: "none", "wide", "narrow", or "mixed" when the plan's sub-batches
+        differ (each goes by the long buffers it has per CU unless ZSC_HIP_SEG_RING says it at plan creation)."""
+        return ("none", "wide", "narrow", "mixed")[lib.zsc_hip_deflate_plan_seg_ring(self._h)]
 
     def profile(self, enable: bool = True) -> None:
         lib.zsc_hip_deflate_plan_profile(self._h, 1 if enable else 0)

@@ -199,7 +199,9 @@ DEV void lz_load_chunk(const LzJob &job, L *lds, LzState &st)
             uint32_t off = k + (uint32_t)LANE * 16u;
             uint32_t a = a0 + off;
             uint8_t *dst = &lds->ring[r0 + off];
-            if (a + 16 <= job.ntot) {
+            if (L::CHUNK % (WAVE * 16u) != 0u && off >= L::CHUNK) {
+                /* (a chunk shorter than a step of the whole wave: the lanes behind it have nothing to bring) */
+            } else if (a + 16 <= job.ntot) {
                 /* 16-byte aligned: buffers start 16-byte aligned in the batch */
                 COPY16(dst, job.in + a);
             } else {

@@ -6,7 +6,7 @@
  * done, one wave resolves (and every parser that gave up costs a round in which one wave parses).
  * None of that waiting is needed by the result: a speculative segment depends on window bytes only,
  * and only the resolver is ordered.  Here the segments of the whole buffer are numbered 0, 1, 2 ...,
- * segment g uses slot g % SG_NS of trace / tkind / wv and of the scratch, and the waves of the
+ * segment g uses slot g % NSLOT of trace / tkind / wv and of the scratch, and the waves of the
  * workgroup never meet between the first and the last segment.  A wave takes the most urgent JOB whose
  * preconditions hold, runs it to the end without waiting for anybody inside it, and comes back:
  *
@@ -26,10 +26,34 @@
  * one window before the first position of the oldest segment that has not given its slot back
  * (sg_pipe_floor).  sg_pipe_may_load is that invariant, stated once; the host emulation asserts the
  * same predicate on every ring read and every chunk load (tests/emu_pipe).  Segment g may start when
- * its slot is free (g < p_released + SG_NS) and the ring holds everything up to the end of what its
+ * its slot is free (g < p_released + NSLOT) and the ring holds everything up to the end of what its
  * parser can touch (sg_pipe_want).  The mirror behind the ring's end is rewritten by the load of the
  * chunk at ring offset 0, whose bytes it repeats (lz_load_chunk): what it held before lies a whole ring
  * back and is covered by the same invariant.
+ *
+ * The geometry (ring, chunk, slots) belongs to the type L the schedule is instantiated with (lz_parse_seg.h):
+ * SgLds, the super-steps' own (45 056 / 2 048 / 32: the slots bound what is in flight), and SgLdsNarrow
+ * (37 888 / 512 / 18: the ring does, and four workgroups fit a CU).  Progress, with rel = p_released and the
+ * numbers of SgLdsNarrow in brackets; every statement is about RING, CHUNK, NSLOT and holds for both:
+ *   - The loader may bring hi up to RING + floor(rel), in whole chunks: RING + rel SG_G - ZD_TILE once the
+ *     window moves, less at most CHUNK - SG_G for the rounding (>= rel SG_G + 4 864).  Segment g wants
+ *     (g + 1) SG_G + SG_OV + 2 ZD_MIN_LOOKAHEAD (rel SG_G + 1 292 for g = rel): the oldest segment that has
+ *     not given its slot back can always be handed out, parsed and parsed again with the ring at its limit,
+ *     whatever the others do -- RING >= ZD_TILE + SG_G + SG_OV + 2 ZD_MIN_LOOKAHEAD + CHUNK is all it takes.
+ *     Its reads go no further back than max_dist (and 15 bytes for the sweep's aligned reads) from a position
+ *     at or above rel SG_G, above the floor, and no further ahead than what it wanted.  [g <= rel + 14: fifteen
+ *     segments in flight, fourteen while rel is odd.  Before the window moves and once the whole input is
+ *     loaded the ring holds nobody back and the slots do.]
+ *   - A parser that runs past its segment looks for a hand-over in the two segments behind its own, as far as
+ *     their slots hold their own traces or none (sg_pipe_limit: below rel + NSLOT, read anew at every step
+ *     past the end).  Beyond that it ends as SG_EXIT_LAST and the segment it stands in is parsed again from
+ *     its exact state: slower, never different.  [rel + 14 + 2 < rel + 18: while the ring is the bound no
+ *     parser ends that way.]
+ *   - A segment to be parsed again (p_redo) waits for the speculative parse of the same segment, which may
+ *     wait for a slot or for the ring: the resolver gives slots back while the redo is pending (the loop
+ *     at the top of sg_pipe_resolve runs before `held` is looked at), rel reaches the chain's segment or the
+ *     first segment not handed out yet, and that one is the oldest unreleased segment of the first point.
+ * SG_PIPE_MAX_IDLE below is the last line of defence behind this argument, not a part of it.
  */
 #ifndef ZSC_LZ_PARSE_PIPE_H
 #define ZSC_LZ_PARSE_PIPE_H
@@ -59,9 +83,10 @@ DEV uint32_t sg_pipe_floor(uint32_t released)
     return a > ZD_TILE ? a - ZD_TILE : 0u;
 }
 /* may the chunk at hi be loaded?  Not before everything it overwrites lies below that byte. */
+template <class L>
 DEV bool sg_pipe_may_load(uint32_t hi, uint32_t released)
 {
-    return (uint64_t)hi + SgLds::CHUNK <= (uint64_t)SgLds::RING + sg_pipe_floor(released);
+    return (uint64_t)hi + L::CHUNK <= (uint64_t)L::RING + sg_pipe_floor(released);
 }
 /* the ring must hold [.., this) before segment g is handed out: its parser runs at most SG_OV past the
  * segment's end and reads a lookahead and what the register caches fetch ahead beyond that */
@@ -89,16 +114,17 @@ DEV bool sg_pipe_claim(uint32_t *word, uint32_t from, uint32_t to)
 }
 
 /* before the first segment (wave 0; the caller puts a barrier behind it) */
-DEV void sg_pipe_init(SgLds *lds, int w)
+template <class L>
+DEV void sg_pipe_init(L *lds, int w)
 {
     sg_init(lds, w);
     if (w != 0)
         return;
     FOR_LANES
     {
-        for (uint32_t i = (uint32_t)LANE; i < SG_NS * (SG_TRACE / 32); i += WAVE)
+        for (uint32_t i = (uint32_t)LANE; i < L::NSLOT * (SG_TRACE / 32); i += WAVE)
             (&lds->trace[0][0])[i] = 0;
-        for (uint32_t i = (uint32_t)LANE; i < SG_NS; i += WAVE)
+        for (uint32_t i = (uint32_t)LANE; i < L::NSLOT; i += WAVE)
             lds->p_done[i] = 0;
     }
     ON_LANE0
@@ -115,7 +141,8 @@ DEV void sg_pipe_init(SgLds *lds, int w)
 }
 
 /* the resolver, by the wave that holds p_res_busy: as far as complete segments allow, then it yields */
-DEV void sg_pipe_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr)
+template <class L>
+DEV void sg_pipe_resolve(const LzJob &job, L *lds, const SgScratch &scr)
 {
     if (UNI(LDS_LOAD_ACQ(&lds->finished)) != 0u)
         return;
@@ -127,11 +154,11 @@ DEV void sg_pipe_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr)
     for (;;) {
         /* slots behind the chain whose parsers are through go back, trace cleared */
         const uint32_t rel0 = rel;
-        while (rel < k && UNI(LDS_LOAD_ACQ(&lds->p_done[rel % SG_NS])) == rel + 1u) {
+        while (rel < k && UNI(LDS_LOAD_ACQ(&lds->p_done[rel % L::NSLOT])) == rel + 1u) {
             FOR_LANES
             {
                 if ((uint32_t)LANE < SG_TRACE / 32)
-                    lds->trace[rel % SG_NS][LANE] = 0;
+                    lds->trace[rel % L::NSLOT][LANE] = 0;
             }
             rel++;
         }
@@ -139,7 +166,7 @@ DEV void sg_pipe_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr)
             WAVE_SYNC();
             ON_LANE0 { LDS_STORE_REL(&lds->p_released, rel); }
         }
-        const uint32_t ks = k % SG_NS;
+        const uint32_t ks = k % L::NSLOT;
         if (held)
             return;
         if (UNI(LDS_LOAD_ACQ(&lds->p_done[ks])) != k + 1u)
@@ -199,15 +226,15 @@ DEV void sg_pipe_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr)
 
 /* One job, if one is ready.  `allow` is SG_JOB_ALL in the product; the host emulation narrows it to
  * drive the same code through other schedules. */
-template <bool TABLE>
-DEV int sg_pipe_step(const LzJob &job, SgLds *lds, const SgScratch &scr, uint32_t allow)
+template <bool TABLE, class L>
+DEV int sg_pipe_step(const LzJob &job, L *lds, const SgScratch &scr, uint32_t allow)
 {
     if (UNI(LDS_LOAD_ACQ(&lds->finished)) != 0u)
         return SG_PIPE_DONE;
     const uint32_t redo = UNI(LDS_LOAD_ACQ(&lds->p_redo));
     if ((allow & SG_JOB_REDO) && redo == 1u) {
         const uint32_t t = UNI(lds->redo_seg);
-        if (UNI(LDS_LOAD_ACQ(&lds->p_done[t % SG_NS])) == t + 1u && sg_pipe_claim(&lds->p_redo, 1u, 2u)) {
+        if (UNI(LDS_LOAD_ACQ(&lds->p_done[t % L::NSLOT])) == t + 1u && sg_pipe_claim(&lds->p_redo, 1u, 2u)) {
             const uint32_t sp = UNI(lds->p_rs[0]), sl = UNI(lds->p_rs[1]), sa = UNI(lds->p_rs[2]);
             const uint32_t sn = UNI(lds->p_rs[3]);
             SG_COUNT(2, 0x10000 + t);
@@ -220,8 +247,8 @@ DEV int sg_pipe_step(const LzJob &job, SgLds *lds, const SgScratch &scr, uint32_
     const uint32_t rel = UNI(LDS_LOAD_ACQ(&lds->p_released));
     if ((allow & SG_JOB_RESOLVE) && UNI(LDS_LOAD_ACQ(&lds->p_res_busy)) == 0u) {
         const uint32_t k = UNI(LDS_LOAD_ACQ(&lds->chain)); /* (a hint: the resolver looks again once it holds the word) */
-        if (((redo == 0u && UNI(LDS_LOAD_ACQ(&lds->p_done[k % SG_NS])) == k + 1u) ||
-             (rel < k && UNI(LDS_LOAD_ACQ(&lds->p_done[rel % SG_NS])) == rel + 1u)) &&
+        if (((redo == 0u && UNI(LDS_LOAD_ACQ(&lds->p_done[k % L::NSLOT])) == k + 1u) ||
+             (rel < k && UNI(LDS_LOAD_ACQ(&lds->p_done[rel % L::NSLOT])) == rel + 1u)) &&
             sg_pipe_claim(&lds->p_res_busy, 0u, 1u)) {
             sg_pipe_resolve(job, lds, scr);
             ON_LANE0 { LDS_STORE_REL(&lds->p_res_busy, 0u); }
@@ -229,16 +256,16 @@ DEV int sg_pipe_step(const LzJob &job, SgLds *lds, const SgScratch &scr, uint32_
         }
     }
     uint32_t hi = UNI(LDS_LOAD_ACQ(&lds->hi));
-    if ((allow & SG_JOB_LOAD) && hi < job.ntot && sg_pipe_may_load(hi, rel) &&
+    if ((allow & SG_JOB_LOAD) && hi < job.ntot && sg_pipe_may_load<L>(hi, rel) &&
         UNI(LDS_LOAD_ACQ(&lds->p_load_busy)) == 0u && sg_pipe_claim(&lds->p_load_busy, 0u, 1u)) {
         hi = UNI(LDS_LOAD_ACQ(&lds->hi)); /* (whoever held the loader before may have moved it) */
-        if (hi < job.ntot && sg_pipe_may_load(hi, rel)) {
+        if (hi < job.ntot && sg_pipe_may_load<L>(hi, rel)) {
             SG_PIPE_HOOK_LOAD(hi, rel);
             LzState st;
             st.hi = hi;
             st.lo = 0;
-            st.wrap_base = hi / SgLds::RING * SgLds::RING;
-            lz_load_chunk<SgLds>(job, lds, st);
+            st.wrap_base = hi / L::RING * L::RING;
+            lz_load_chunk<L>(job, lds, st);
             ON_LANE0 { LDS_STORE_REL(&lds->hi, st.hi); }
         }
         ON_LANE0 { LDS_STORE_REL(&lds->p_load_busy, 0u); }
@@ -246,12 +273,12 @@ DEV int sg_pipe_step(const LzJob &job, SgLds *lds, const SgScratch &scr, uint32_
     }
     if (allow & SG_JOB_PARSE) {
         const uint32_t g = UNI(LDS_LOAD_ACQ(&lds->p_next));
-        if (g < sg_pipe_nseg(job.n) && g < rel + SG_NS && hi >= sg_pipe_want(g, job.ntot) &&
+        if (g < sg_pipe_nseg(job.n) && g < rel + L::NSLOT && hi >= sg_pipe_want(g, job.ntot) &&
             sg_pipe_claim(&lds->p_next, g, g + 1u)) {
             SG_COUNT(2, g);
             sg_parse_segment<TABLE, true>(job, lds, scr, g, g * SG_G, 2u, 0u, 0);
             SG_COUNT(3, 0);
-            ON_LANE0 { LDS_STORE_REL(&lds->p_done[g % SG_NS], g + 1u); }
+            ON_LANE0 { LDS_STORE_REL(&lds->p_done[g % L::NSLOT], g + 1u); }
             return SG_PIPE_WORKED;
         }
     }
@@ -260,7 +287,8 @@ DEV int sg_pipe_step(const LzJob &job, SgLds *lds, const SgScratch &scr, uint32_
 
 #ifndef ZSC_WAVE_EMU
 /* how far the workgroup has got, as one number: every job that ends moves one of these */
-DEV uint32_t sg_pipe_progress(SgLds *lds)
+template <class L>
+DEV uint32_t sg_pipe_progress(L *lds)
 {
     return UNI(LDS_LOAD_ACQ(&lds->p_next)) + UNI(LDS_LOAD_ACQ(&lds->p_released)) + UNI(LDS_LOAD_ACQ(&lds->hi)) +
            UNI(LDS_LOAD_ACQ(&lds->chain)) + UNI(LDS_LOAD_ACQ(&lds->p_redo));
@@ -279,8 +307,8 @@ DEV uint32_t sg_pipe_progress(SgLds *lds)
  * (longer when it keeps finding none) and asks again.  Waves only wait for waves of their own
  * workgroup, and the number of empty polls without any progress in the workgroup is bounded, so that a
  * logic error ends as Z_STREAM_ERROR (p_stuck) instead of hanging the device. */
-template <bool TABLE>
-DEV void sg_pipe_run(const LzJob &job, SgLds *lds, const SgScratch &scr)
+template <bool TABLE, class L>
+DEV void sg_pipe_run(const LzJob &job, L *lds, const SgScratch &scr)
 {
     uint32_t idle = 0, row = 0, seen = 0;
     for (;;) {

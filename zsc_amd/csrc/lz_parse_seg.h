@@ -65,7 +65,7 @@
 #define SG_SPAN 8192u               /* positions per super-step */
 #endif
 #ifndef SG_MIN_WAVES
-#define SG_MIN_WAVES 6 /* waves per SIMD the register allocation aims at (three workgroups per CU) */
+#define SG_MIN_WAVES 6 /* waves per SIMD the register allocation of k_parse_seg aims at: SgLds (49 392 bytes) puts three workgroups on a CU.  The narrow entry has its own, SG_NARROW_MIN_WAVES */
 #endif
 #define SG_NS (SG_SPAN / SG_G)      /* segments per super-step, handed to the waves by a work queue */
 #ifndef SG_OV
@@ -126,17 +126,34 @@ typedef struct {
     uint32_t ntok;                                  /* tokens its parser emitted */
 } SgWave;
 
-struct SgLds {
-    /* window (32 KiB back) + one super-step + overlap + two lookaheads + one chunk being
-     * loaded, in whole chunks: 45056 for the default super-step */
-    static constexpr uint32_t CHUNK = 2048u;
-    static constexpr uint32_t RING = (ZD_TILE + SG_SPAN + SG_OV + 2u * ZD_MIN_LOOKAHEAD + 2u * CHUNK - 1u) / CHUNK * CHUNK;
+/* The LDS of one workgroup.  Its geometry -- the window ring, the chunk the ring is loaded in, and the
+ * number of slots of trace / tkind / wv / p_done -- is a property of the type, and the parser and both
+ * schedules are instantiated with it:
+ *   SgLds        the super-steps' (SG_NS slots, one per segment of a super-step, and a ring that holds a
+ *                whole super-step in front of the window); the pipeline runs in it as well
+ *   SgLdsNarrow  the pipeline's own (lz_parse_pipe.h): no super-step in the ring, 18 slots -- four
+ *                workgroups on a CU in place of three
+ * PAD: bytes of a dead array (a measurement control, SG_NARROW_PAD below). */
+template <uint32_t PAD>
+struct SgLdsPad {
+    uint32_t dead[PAD / 4u];
+};
+template <>
+struct SgLdsPad<0u> {
+};
+template <uint32_t RING_, uint32_t CHUNK_, uint32_t NSLOT_, uint32_t PAD_ = 0u>
+struct SgLdsT : SgLdsPad<PAD_> {
+    static constexpr uint32_t CHUNK = CHUNK_;
+    static constexpr uint32_t RING = RING_;
+    static constexpr uint32_t NSLOT = NSLOT_; /* slots; in the pipeline segment g uses slot g % NSLOT */
     static constexpr bool HAS_INS = false;
     static constexpr bool GLOBAL_WIN = false;
+    static_assert(RING_ % CHUNK_ == 0u && CHUNK_ % 256u == 0u && CHUNK_ >= LZ_MIRROR, "the ring is loaded in whole chunks, the mirror by the chunk at its start");
+    static_assert(NSLOT_ <= SG_NS, "the scratch in memory is laid out for SG_NS slots");
     uint8_t ring[RING + 512];
-    uint32_t trace[SG_NS][SG_TRACE / 32];
-    uint32_t tkind[SG_NS][SG_TRACE / 32]; /* for the positions in trace: 1 = a literal was owed there */
-    SgWave wv[SG_NS];             /* one record per segment of the super-step */
+    uint32_t trace[NSLOT][SG_TRACE / 32];
+    uint32_t tkind[NSLOT][SG_TRACE / 32]; /* for the positions in trace: 1 = a literal was owed there */
+    SgWave wv[NSLOT];             /* one record per segment of the super-step */
     /* workgroup state */
     uint32_t S0;                  /* first position of the current super-step */
     uint32_t finished;
@@ -148,8 +165,8 @@ struct SgLds {
     SgOut out;
     uint32_t cstage[WAVE];
     /* the pipeline schedule (lz_parse_pipe.h): segments are numbered through the whole buffer and
-     * segment g uses slot g % SG_NS of trace / tkind / wv and of the scratch */
-    uint32_t p_done[SG_NS];       /* g + 1 once the speculative parse of segment g is complete */
+     * segment g uses slot g % NSLOT of trace / tkind / wv and of the scratch */
+    uint32_t p_done[NSLOT];       /* g + 1 once the speculative parse of segment g is complete */
     uint32_t p_next;              /* next segment to hand out */
     uint32_t p_released;          /* every segment below this one has given its slot back */
     uint32_t p_res_busy, p_load_busy; /* the resolver / the window loader is at work */
@@ -159,6 +176,23 @@ struct SgLds {
                                      read from sidx once that segment is complete); 0xffffffff: chain_ft holds */
     uint32_t p_stuck;
 };
+/* window (32 KiB back) + one super-step + overlap + two lookaheads + one chunk being
+ * loaded, in whole chunks: 45056 for the default super-step */
+typedef SgLdsT<(ZD_TILE + SG_SPAN + SG_OV + 2u * ZD_MIN_LOOKAHEAD + 2u * 2048u - 1u) / 2048u * 2048u, 2048u, SG_NS> SgLds;
+/* The pipeline alone: one window behind the oldest segment that has not given its slot back (rel), the
+ * hand-over margin of the newest one in flight and the chunks loaded so far (sg_pipe_may_load: hi <= RING +
+ * rel SG_G - ZD_TILE; sg_pipe_want: hi >= (g + 1) SG_G + 1 036).  With 37 888 bytes that is g <= rel + 14, fifteen
+ * segments in flight (fourteen while rel is odd: hi moves in chunks of 512).  A parser looks into the two
+ * segments behind its own, so 18 slots (rel + 16 < rel + NSLOT) and not 16: once the window moves the ring, not
+ * the slots, is what holds a segment back, and no parser ends for want of a slot (lz_parse_pipe.h has the
+ * argument).  40 712 bytes in all: four workgroups in a CU's 160 KiB (40 960 each). */
+#ifdef SG_NARROW_PAD /* a measurement control: the narrow geometry at the wide one's size, three workgroups per CU */
+#define SG_NARROW_PAD_BYTES (45056u - 37888u + (SG_NS - 18u) * 108u)
+#else
+#define SG_NARROW_PAD_BYTES 0u
+#endif
+typedef SgLdsT<37888u, 512u, 18u, SG_NARROW_PAD_BYTES> SgLdsNarrow;
+#define SG_NARROW_MIN_WAVES 8 /* waves per SIMD the narrow entry's register allocation aims at (four workgroups per CU) */
 
 /* scratch in HBM per workgroup */
 typedef struct {
@@ -220,11 +254,11 @@ DEV uint32_t sg_nact(uint32_t S0, uint32_t n)
 }
 
 /* phase 1 (wave 0): slide the window to the new super-step, fill the work queue */
-DEV void sg_phase_begin(const LzJob &job, SgLds *lds, int w)
+template <class L>
+DEV void sg_phase_begin(const LzJob &job, L *lds, int w)
 {
     if (w != 0)
         return;
-    typedef SgLds L;
     LzState st;
     st.lo = UNI(lds->lo);
     st.hi = UNI(lds->hi);
@@ -246,7 +280,7 @@ DEV void sg_phase_begin(const LzJob &job, SgLds *lds, int w)
     }
     FOR_LANES
     {
-        for (uint32_t i = (uint32_t)LANE; i < SG_NS * (SG_TRACE / 32); i += WAVE)
+        for (uint32_t i = (uint32_t)LANE; i < L::NSLOT * (SG_TRACE / 32); i += WAVE)
             (&lds->trace[0][0])[i] = 0;
     }
     WAVE_SYNC();
@@ -257,15 +291,17 @@ DEV void sg_phase_begin(const LzJob &job, SgLds *lds, int w)
  * The ring holds position x at x % RING, whatever has been loaded since (lz_load_chunk keeps it so).  A
  * parser that starts at p reads [p - wsize, p + SG_G + SG_OV + a lookahead or two): with the multiple of
  * RING at or below p - wsize as its base, lz_ridx's one conditional wrap serves for all of them. */
+template <class L>
 DEV uint32_t sg_pipe_wrap_base(uint32_t p)
 {
-    return p > ZD_TILE ? (p - ZD_TILE) / SgLds::RING * SgLds::RING : 0u;
+    return p > ZD_TILE ? (p - ZD_TILE) / L::RING * L::RING : 0u;
 }
 /* A parser that has run past its segment may look for a hand-over in the segments whose slots hold their
- * own traces or none yet: those below p_released + SG_NS (a slot is cleared before it is given back). */
-DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
+ * own traces or none yet: those below p_released + NSLOT (a slot is cleared before it is given back). */
+template <class L>
+DEV uint32_t sg_pipe_limit(L *lds, uint32_t n)
 {
-    const uint64_t e = ((uint64_t)GUNI(LDS_LOAD_ACQ(&lds->p_released)) + SG_NS) * SG_G;
+    const uint64_t e = ((uint64_t)GUNI(LDS_LOAD_ACQ(&lds->p_released)) + L::NSLOT) * SG_G;
     return e < n ? (uint32_t)e : n;
 }
 
@@ -907,24 +943,23 @@ DEV uint32_t sg_pipe_limit(SgLds *lds, uint32_t n)
 /* parse from (p, cur_len, cur_at, pending) -- a state of the serial parse, or the fresh
  * state at the start of segment s -- until the parse can be handed to a later segment's
  * tokens, gives up, or leaves the super-step */
-/* PIPE (lz_parse_pipe.h): s is the segment's number in the whole buffer, its slot is s % SG_NS, the
+/* PIPE (lz_parse_pipe.h): s is the segment's number in the whole buffer, its slot is s % NSLOT, the
  * super-step is the whole buffer as far as slots have been given back, and the ring index is taken
  * from the parser's own start so that it holds while the window slides under it */
-template <bool TABLE, bool PIPE = false> /* TABLE: the buffer has a match table (job.r2): a build without it carries none of its code */
-DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, uint32_t s,
+template <bool TABLE, bool PIPE = false, class L = SgLds> /* TABLE: the buffer has a match table (job.r2): a build without it carries none of its code */
+DEV void sg_parse_segment(const LzJob &job, L *lds, const SgScratch &scr, uint32_t s,
                           uint32_t p, uint32_t cur_len, uint32_t cur_at, int pending)
 {
-    typedef SgLds L;
     LzState st;
     st.lo = GUNI(lds->lo);
     st.hi = GUNI(lds->hi);
-    st.wrap_base = PIPE ? sg_pipe_wrap_base(p) : GUNI(lds->wrap_base);
+    st.wrap_base = PIPE ? sg_pipe_wrap_base<L>(p) : GUNI(lds->wrap_base);
     st.nsyms = st.nstaged = st.nblocks = st.blk_sym0 = st.blk_in0 = st.pr_hi = 0;
     st.n = job.n;
     st.si = 0;
     st.it = 0;
 
-    const uint32_t slot = PIPE ? s % SG_NS : s;
+    const uint32_t slot = PIPE ? s % L::NSLOT : s;
     const uint32_t S0 = PIPE ? 0u : GUNI(lds->S0);
     const uint64_t E64 = (uint64_t)S0 + SG_SPAN;
     /* end of the super-step (PIPE: read when the parser leaves its segment, it only grows) */
@@ -1000,7 +1035,7 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
                 /* the segment p lies in recorded the positions its own parser was fresh at */
                 const uint32_t t = (p - S0) / SG_G, r = (p - S0) % SG_G;
                 /* (the other parser may still be running: its words are published kinds first) */
-                const uint32_t ts = PIPE ? t % SG_NS : t;
+                const uint32_t ts = PIPE ? t % L::NSLOT : t;
                 const uint32_t tword = GUNI(LDS_LOAD_ACQ(&lds->trace[ts][r >> 5]));
                 if (((tword >> (r & 31u)) & 1u) &&
                     ((GUNI(lds->tkind[ts][r >> 5]) >> (r & 31u)) & 1u) == (uint32_t)pending) {
@@ -1556,8 +1591,8 @@ DEV void sg_parse_segment(const LzJob &job, SgLds *lds, const SgScratch &scr, ui
  * parsed, so it finds a hand-over.  Segment 0 starts from the state the previous
  * super-step ended in, every other one fresh.  In a redo round (phase 3 found a parser
  * that gave up) wave 0 parses on from that parser's exact state. */
-template <bool TABLE>
-DEV void sg_phase_parse(const LzJob &job, SgLds *lds, const SgScratch &scr, int w)
+template <bool TABLE, class L>
+DEV void sg_phase_parse(const LzJob &job, L *lds, const SgScratch &scr, int w)
 {
     const uint32_t S0 = GUNI(lds->S0);
     const uint32_t nact = sg_nact(S0, job.n);
@@ -1685,7 +1720,8 @@ DEV void sg_append(const LzJob &job, SgOut *o, const uint32_t *tok, uint32_t fro
 
 /* the parse reached the end of the input at xp (src/deflate.c:2108-2117): the owed literal, the last
  * block, and the counts the later kernels read (by the one wave that is resolving) */
-DEV void sg_end_of_input(const LzJob &job, SgLds *lds, uint32_t pending, uint32_t xp)
+template <class L>
+DEV void sg_end_of_input(const LzJob &job, L *lds, uint32_t pending, uint32_t xp)
 {
     if (pending) {
         /* the last byte goes out as a literal; _tr_tally's "block full" answer is
@@ -1724,7 +1760,8 @@ DEV void sg_end_of_input(const LzJob &job, SgLds *lds, uint32_t pending, uint32_
 
 /* phase 3 (wave 0): follow the chain of hand-overs from segment 0 and collect the
  * tokens; where a parser gave up, ask for a redo round and come back */
-DEV void sg_phase_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr, int w)
+template <class L>
+DEV void sg_phase_resolve(const LzJob &job, L *lds, const SgScratch &scr, int w)
 {
     if (w != 0)
         return;
@@ -1784,7 +1821,8 @@ DEV void sg_phase_resolve(const LzJob &job, SgLds *lds, const SgScratch &scr, in
  * the window and the output carried over.  A joint of kind 0 only changes n, and nothing the
  * parse did before it depends on n when the cut lies MIN_LOOKAHEAD or more before the old end
  * (sections.h sec_seg_ok; the others go to the wave-per-buffer parser). */
-DEV void sg_next_phase(SgLds *lds, int w, uint32_t from)
+template <class L>
+DEV void sg_next_phase(L *lds, int w, uint32_t from)
 {
     if (w != 0)
         return;
@@ -1815,7 +1853,8 @@ DEV uint32_t sg_phase_end(const LzJob &job, uint32_t n_now, uint32_t *si)
 }
 
 /* before the first super-step (wave 0) */
-DEV void sg_init(SgLds *lds, int w)
+template <class L>
+DEV void sg_init(L *lds, int w)
 {
     if (w != 0)
         return;

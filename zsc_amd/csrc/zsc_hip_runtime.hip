@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -437,6 +438,76 @@ __global__ __launch_bounds__(SG_W * 64, SG_MIN_WAVES) void k_parse_seg(const uin
         __syncthreads();
     }
     if (stuck && threadIdx.x == 0) {
+        job.out->nsyms = 0;
+        job.out->nblocks = 0xffffffffu; /* reported as Z_STREAM_ERROR by the layout kernel */
+    }
+}
+
+/* k_parse_seg for plain buffers in the pipeline schedule, in the pipeline's own LDS geometry (SgLdsNarrow,
+ * lz_parse_seg.h): 40 712 bytes of LDS and registers for eight waves per SIMD put four workgroups on a CU.
+ * Built without the match table and for window_bits 15 / mem_level 8 only; launched for plans without joints
+ * (every buffer is a plain one), so there is no super-step path in it. */
+template <int LEVEL>
+__global__ __launch_bounds__(SG_W * 64, SG_NARROW_MIN_WAVES) void k_parse_seg_narrow(const uint8_t *__restrict__ in,
+                                                         const ZdBuf *__restrict__ bufs,
+                                                         const uint32_t *__restrict__ order,
+                                                         const uint32_t *__restrict__ sorted,
+                                                         const uint16_t *__restrict__ rank,
+                                                         const uint16_t *__restrict__ hib,
+                                                         const uint32_t *__restrict__ cnt,
+                                                         const uint16_t *__restrict__ dir,
+                                                         uint32_t *__restrict__ syms,
+                                                         ZdBlockRec *__restrict__ recs,
+                                                         ZdParseOut *__restrict__ pout,
+                                                         uint32_t *__restrict__ seg_tok,
+                                                         const ZdLevel cfg, uint32_t stair_min,
+                                                         uint32_t first, uint32_t nbuf)
+{
+    __shared__ SgLdsNarrow lds;
+    if (blockIdx.x >= nbuf)
+        return;
+    const uint32_t b = order[first + blockIdx.x];
+    const ZdBuf buf = bufs[b];
+    LzJob job;
+    job.in = in + buf.in_off;
+    job.n = buf.in_len;
+    job.ntot = buf.in_len;
+    job.sorted = sorted + (uint64_t)buf.tile0 * ZD_TILE;
+    job.rank = rank + buf.rank_off;
+    job.hib = hib + buf.rank_off;
+    job.cnt = cnt + buf.rank_off;
+    job.dir = dir ? dir + (uint64_t)buf.tile0 * ZD_DIR_STRIDE : nullptr;
+    job.r2 = nullptr;
+    job.stair_min = stair_min;
+    job.syms = syms + buf.sym_off;
+    job.blocks = recs + buf.blk0;
+    job.out = pout + b;
+    job.cfg = cfg;
+    job.cfg.wsize = ZD_TILE;
+    job.cfg.max_dist = ZD_MAX_DIST;
+    job.cfg.sym_cap = ZD_SYM_CAP;
+    job.cfg.hbits = 15u;
+    if (LEVEL == 6) { /* (as k_parse_seg) */
+        job.cfg.good = 8;
+        job.cfg.lazy = 16;
+        job.cfg.nice = 128;
+        job.cfg.chain = 128;
+        job.cfg.slow = 1;
+    }
+    job.strategy = LEVEL == 6 ? 0u : buf.strategy;
+    job.more = buf.more;
+    job.sched = nullptr;
+    job.nsched = 0;
+    job.n0 = buf.n0;
+    SgScratch scr;
+    /* (the scratch keeps the layout of SG_NS slots; this geometry uses the first SgLdsNarrow::NSLOT of each part) */
+    scr.tok = seg_tok + (uint64_t)blockIdx.x * SG_SCRATCH_WORDS;
+    scr.sidx = (uint16_t *)(scr.tok + SG_NS * SG_TOKCAP);
+    sg_pipe_init(&lds, (int)(threadIdx.x >> 6));
+    __syncthreads();
+    sg_pipe_run<false>(job, &lds, scr);
+    __syncthreads();
+    if (lds.p_stuck && threadIdx.x == 0) {
         job.out->nsyms = 0;
         job.out->nblocks = 0xffffffffu; /* reported as Z_STREAM_ERROR by the layout kernel */
     }
@@ -1394,6 +1465,7 @@ struct SubBatch {
      * [0,c36) full ring, [c36,c16) <= 18 432 B, [c16,c8) <= 10 240 B, [c8,count) <= 6 144 B */
     uint32_t c36 = 0, c16 = 0, c8 = 0;
     uint32_t cseg = 0;  /* [0,cseg) of the length-sorted order go to the segmented parser */
+    bool seg_narrow = false; /* ... in the pipeline's own LDS geometry (k_parse_seg_narrow); fixed when the plan is made */
 };
 
 /* Packing (pack.h): what a plan of either kind holds for it, and the launches */
@@ -1603,6 +1675,8 @@ struct zsc_hip_deflate_plan {
     /* read from the environment once, when the plan is made (A/B and debugging): a plan cannot get a mixed
      * configuration and the launch path looks nothing up */
     bool seg_pipe = true;     /* ZSC_HIP_SEG_PIPE=0: plain buffers in super-steps too (lz_parse_seg.h) */
+    int seg_ring_said = 0;    /* ZSC_HIP_SEG_RING: 1 wide, 2 narrow, 0 nothing said -- each sub-batch goes by the workgroups
+                                 it offers a CU (SubBatch::seg_narrow) */
     bool link_kernel = false; /* ZSC_HIP_LINK_KERNEL: k_link_prev runs even where the parser could do without */
     bool fast_ring = false;   /* ZSC_HIP_FAST_RING: levels 1-3 with the window in an LDS ring */
     DevBuf d_res; /* one ZdResult per buffer of the whole plan */
@@ -1649,6 +1723,28 @@ struct zsc_hip_deflate_plan {
     /* packing (pack.h), off unless zsc_hip_deflate_plan_pack_enable was called */
     PackState pack;
 };
+
+/* The LDS geometry the pipeline runs in when nothing is said (ZSC_HIP_SEG_RING).  The narrow ring pays through
+ * the fourth workgroup on a CU and costs through the shorter pipeline (+4.2 % on the
+ * headline; 2 to 21 % slower, by class, where a CU is offered three workgroups or fewer), so a sub-batch takes it
+ * when it has more long buffers than three per CU, each sub-batch for itself. */
+#define ZSC_SEG_WIDE_WG_PER_CU 3u
+
+/* is the plan one k_parse_seg_narrow is built for?  Plain buffers in the pipeline schedule that would otherwise
+ * take k_parse_seg<false, false, 6 or 0> */
+static bool zsc_plan_narrow_able(const zsc_hip_deflate_plan *pl)
+{
+    return pl->use_seg && pl->seg_pipe && pl->d_sched.p == nullptr && !pl->use_table && pl->wbits == 15 &&
+           pl->mem_level == 8;
+}
+/* sub-batches of the plan whose segmented parser runs in the narrow geometry, and in the wide one */
+static void zsc_plan_seg_rings(const zsc_hip_deflate_plan *pl, uint32_t *wide, uint32_t *narrow)
+{
+    *wide = *narrow = 0;
+    for (const SubBatch &sb : pl->subs)
+        if (pl->use_seg && sb.cseg > 0)
+            (sb.seg_narrow && zsc_plan_narrow_able(pl) ? *narrow : *wide)++;
+}
 
 namespace {
 void ensure_init()
@@ -1915,6 +2011,8 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
     pl->use_seg = getenv("ZSC_HIP_NO_SEG") == nullptr && kLevels[level].slow;
     if (const char *e = getenv("ZSC_HIP_SEG_PIPE"))
         pl->seg_pipe = atoi(e) != 0;
+    if (const char *e = getenv("ZSC_HIP_SEG_RING"))
+        pl->seg_ring_said = strcmp(e, "narrow") == 0 ? 2 : strcmp(e, "wide") == 0 ? 1 : 0;
     pl->link_kernel = getenv("ZSC_HIP_LINK_KERNEL") != nullptr;
     pl->fast_ring = getenv("ZSC_HIP_FAST_RING") != nullptr;
     /* per-sub-batch descriptor arrays */
@@ -1953,6 +2051,8 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
             while (k < sb.count && seg_able(order[k]))
                 k++;
             sb.cseg = k;
+            sb.seg_narrow = pl->seg_ring_said == 2 ||
+                            (pl->seg_ring_said == 0 && sb.cseg > ZSC_SEG_WIDE_WG_PER_CU * (uint32_t)g_cus);
             while (k < sb.count && (full_only || len_at(k) > 18432u))
                 k++;
             sb.c36 = k;
@@ -2179,7 +2279,14 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
                        (const uint32_t *)sb.d_order.p, (const uint32_t *)sorted,                 \
                        (const uint16_t *)rank, (const uint16_t *)hib, tmp_syms, recs, pout,      \
                        (const ZdSched *)pl->d_sched.p, cfg, (uint32_t)(FIRST), (uint32_t)(COUNT))
-            if (sb.cseg > 0) {
+            if (sb.cseg > 0 && sb.seg_narrow && zsc_plan_narrow_able(pl)) {
+                hipLaunchKernelGGL(pl->level == 6 && pl->strategy != (uint32_t)Z_FILTERED ? k_parse_seg_narrow<6> : k_parse_seg_narrow<0>,
+                                   dim3(sb.cseg), dim3(SG_W * 64), 0, st, in, bufs,
+                                   (const uint32_t *)sb.d_order.p, (const uint32_t *)sorted,
+                                   (const uint16_t *)rank, (const uint16_t *)hib,
+                                   (const uint32_t *)cnt, link_in_parser ? (const uint16_t *)dir : nullptr, tmp_syms, recs,
+                                   pout, (uint32_t *)pl->d_seg_tok.p, cfg, pl->stair_min, 0u, sb.cseg);
+            } else if (sb.cseg > 0) {
                 auto kern = (pl->wbits == 15 && pl->mem_level == 8)
                                 ? (pl->use_table ? k_parse_seg<false, true, 0>
                                                  : pl->level == 6 && pl->strategy != (uint32_t)Z_FILTERED ? k_parse_seg<false, false, 6>
@@ -2316,6 +2423,15 @@ extern "C" uint64_t zsc_hip_deflate_plan_scratch_bytes(const zsc_hip_deflate_pla
 extern "C" U32 zsc_hip_deflate_plan_sub_batches(const zsc_hip_deflate_plan *pl)
 {
     return pl ? (U32)pl->subs.size() : 0;
+}
+
+extern "C" I32 zsc_hip_deflate_plan_seg_ring(const zsc_hip_deflate_plan *pl)
+{
+    if (!pl || !pl->use_seg)
+        return 0;
+    uint32_t wide, narrow;
+    zsc_plan_seg_rings(pl, &wide, &narrow);
+    return narrow == 0 ? 1 : wide == 0 ? 2 : 3;
 }
 
 extern "C" I32 zsc_hip_deflate_plan_seg_schedule(const zsc_hip_deflate_plan *pl)
@@ -2969,6 +3085,9 @@ namespace {
 
 /* runs the kernels for the runs sections.h wants parsed (one plan per round) and keeps every
  * round's compressed bytes until the streams are put together */
+/* the last sections call of this process: sub-batches parsed in the wide and in the narrow LDS geometry */
+static std::atomic<uint32_t> g_sections_last_rings[2];
+
 struct HipSecRunner {
     const uint8_t *d_src = nullptr; /* the streams' input, stream i at src_off[i] */
     const uint64_t *src_off = nullptr;
@@ -2981,6 +3100,7 @@ struct HipSecRunner {
     };
     std::vector<Round *> rounds;
     uint32_t parses = 0;
+    uint32_t subs_wide = 0, subs_narrow = 0; /* the rounds' sub-batches by the LDS geometry of their segmented parser */
     ZlibReturn error = Z_OK;
     const std::vector<SecStream> *streams = nullptr; /* whose runs say which rounds' bytes are still in use */
     uint64_t parsed_bytes = 0, budget_bytes = ~0ull;  /* work budget: input bytes parsed over all rounds */
@@ -3126,6 +3246,12 @@ struct HipSecRunner {
                                     caps.data() + g0, level, -wbits, mem_level, strategy, &pr);
         if (rc != Z_OK)
             return rc;
+        {
+            uint32_t wide, narrow;
+            zsc_plan_seg_rings(pl, &wide, &narrow);
+            subs_wide += wide;
+            subs_narrow += narrow;
+        }
         DevBuf d_pieces;
         std::vector<ZdStorePiece> gather(count);
         for (U32 j = 0; j < count; j++) {
@@ -3366,10 +3492,20 @@ static ZlibReturn sections_on_device(U32 count, const uint8_t *d_src, const uint
                 std::chrono::duration<double, std::milli>(t_end - t_parsed).count(), (unsigned)runner.rounds.size(),
                 (unsigned long long)runner.parsed_bytes, (unsigned long long)runner.held_peak);
     }
+    g_sections_last_rings[0] = runner.subs_wide;
+    g_sections_last_rings[1] = runner.subs_narrow;
     d_sbufs.release();
     d_sres.release();
     d_pieces.release();
     return rc;
+}
+
+extern "C" void zsc_hip_compress_sections_last_rings(U32 *wide, U32 *narrow)
+{
+    if (wide)
+        *wide = g_sections_last_rings[0];
+    if (narrow)
+        *narrow = g_sections_last_rings[1];
 }
 
 extern "C" ZlibReturn zsc_hip_compress_sections_device(U32 count, const void *d_input,
