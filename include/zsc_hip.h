@@ -467,6 +467,75 @@ ZlibReturn zsc_hip_inflate_plan_check_values(zsc_hip_inflate_plan *plan, U32 *va
 ZlibReturn zsc_hip_uncompress_check_batch(U32 count, const U8 *const *sources, U32 *source_lens,
                                           U32 *dest_lens, I32 *statuses, U32 *check_values, I32 window_bits);
 
+/* Members plans: multi-member gzip files -- the output of zsc_hip_deflate_plan_pack with align 1 over a gzip
+ * plan, BGZF, `cat a.gz b.gz`, pigz -i -- inflated member by member, in parallel
+ * (zsc_amd/csrc/inflate_members.h).  Every other inflate plan, like zsc_uncompress, stops at the end of the
+ * first member.  Arguments as zsc_hip_inflate_plan_create; item i is one file, source_lens[i] bytes at
+ * src_offsets[i], decoded to [dst_offsets[i], + dest_caps[i]).  window_bits must select the gzip wrapper
+ * (16 + 8 .. 16 + 15); anything else, and an unknown flag, is Z_STREAM_ERROR.  Files above 4 GiB of input or
+ * output are not served (the lengths are U32).
+ *
+ * The contract.  The result of file i is that of this walk:
+ *     at = 0; out = 0; members = 0
+ *     loop: (rc, len, used) = what a plain plan (zsc_hip_inflate_plan_create) reports for the stream
+ *                             file[at:] with dest cap dest_caps[i] - out and the plan's window_bits
+ *           out += len; at += used
+ *           if rc != Z_OK: return (rc, out, at, members)
+ *           members += 1
+ *           if fewer than 2 bytes remain at `at`, or they are not 1f 8b: return (Z_OK, out, at, members)
+ * Status, dest_len and consumed (_results) are the walk's rc, out and at.  A file stops at its first member
+ * that is not Z_OK; that member's salvaged bytes are counted, and its inflateSync resynchronisation is what
+ * the plain plan does on file[at:] (zsc_hip_inflate_plan_data_errors reports that member's count).  Zero
+ * padding or other bytes behind the last member end the file with Z_OK; consumed says where.  Nothing outside
+ * a file's own [dst_offsets[i], + dest_caps[i]) is written, whatever the file holds, and nothing is read
+ * outside [src_offsets[i], + source_lens[i]) plus the 64 readable bytes every inflate input has behind it.
+ *
+ * A run scans the files for 1f 8b 08 with the reserved FLG bits clear (candidate member starts), decodes
+ * every candidate as one whole member with nothing stored, follows the chain of clean members from offset 0
+ * while it stays inside dest_caps[i], decodes every chained member again into its place with the plain
+ * decode, and keeps the verified prefix: the chain entries before the first one whose second decode did not
+ * give Z_OK with exactly the counted length and end.  A file whose prefix reaches the walk's end is finished;
+ * every other file -- a member that is not Z_OK, a short dest_caps[i], a header the scan does not take for
+ * one (a method other than 8, reserved FLG bits), more than source_len / 16 + 8 candidates or a used-up
+ * candidate pool (prefix 0), a count pass that has decoded more than 4 * source_len + 64 KiB input bytes of
+ * the file's candidates (prefix 0; a gzip file stored inside a gzip member makes candidates off the chain) --
+ * is taken up by one lane group at the end of its verified prefix and walked serially to its end.
+ *   Claims.  A member whose FEXTRA holds a subfield `B` `C` of length 2 says how long it is (BSIZE + 1, the
+ *   BGZF convention).  Where that end lies inside the file and the ISIZE in front of it is at most 65 536,
+ *   the first decode is skipped and stop and length are taken from the header and trailer.  A claim is never
+ *   trusted: the second decode runs in a slice of exactly the claimed length and must reproduce length and
+ *   end, or the verified prefix ends in front of that member.  So a BGZF file is decoded once, any other file
+ *   twice.  The environment variable ZSC_HIP_MEMBERS_CLAIMS=0, read when the plan is created, switches
+ *   claims off (a test hook and the A/B switch); results do not depend on it.
+ *
+ * flags: 0, or ZSC_HIP_MEMBERS_SIZE_ONLY: nothing is written and d_dst is ignored (it may be NULL), as are
+ * dst_offsets; dest_caps are limits (NULL: 0xFFFFFFFF for every file).  Each member of the walk then follows
+ * the size plan's contract instead of the plain plan's, with its one exception: the CRC-32 is not compared, so
+ * a member whose only fault is its CRC-32 is Z_OK and the walk goes on.  Size-only mode does not use claims:
+ * every member is decoded (once), never trusted -- there is no second decode to hold a claim against.
+ *
+ * _run, _results, _destroy, zsc_hip_inflate_plan_scratch_bytes, zsc_hip_inflate_plan_data_errors and
+ * zsc_hip_inflate_plan_pack_enable / _pack (not in size-only mode) work on it;
+ * zsc_hip_inflate_plan_index_enable returns Z_STREAM_ERROR.  zsc_hip_inflate_plan_sections reports the
+ * verified prefix: the members decoded by the parallel path.  kernel_ms of _results covers all launches of
+ * a run; _results relaunches nothing.  Scratch, held from create to destroy: 28 bytes (size-only: 24) per
+ * slot of one candidate pool of (sum of source_lens) / 256 + 65 536 slots, taken at run time by the files'
+ * candidates, 16 bytes per 4 KiB of input, and 116 bytes per file plus 16.  A plan of any other kind
+ * allocates, launches and returns what it did without members plans. */
+#define ZSC_HIP_MEMBERS_SIZE_ONLY 1u
+ZlibReturn zsc_hip_inflate_plan_create_members(zsc_hip_inflate_plan **plan, U32 count,
+                                               const U32 *source_lens, const uint64_t *src_offsets,
+                                               const U32 *dest_caps, const uint64_t *dst_offsets,
+                                               I32 window_bits, U32 flags);
+/* after _results, of a members plan (Z_STREAM_ERROR for any other): per file, the walk's member count (the
+ * members that were Z_OK) and how many members of the verified prefix were claimed.  Either may be NULL. */
+ZlibReturn zsc_hip_inflate_plan_members(zsc_hip_inflate_plan *plan, U32 *members, U32 *claimed);
+/* zsc_hip_uncompress_batch through a members plan: the same signature and per-item semantics, every source
+ * a multi-member file; members (may be NULL): out, the walk's member count per file */
+ZlibReturn zsc_hip_uncompress_members_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                            U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                            I32 window_bits, U32 *members);
+
 /* seek-point indexes -------------------------------------------------------- */
 
 /* A chunks plan finds, on every run, where the chained pieces of a stream start, how long each one's

@@ -16,6 +16,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
   size-allocate-inflate sequence in one call;
 * :func:`uncompress_check_batch` -- are the streams intact?  Status, length, consumed and the check value of
   every stream, found on the device without writing any output (``InflatePlan(..., check_only=True)``);
+* :func:`uncompress_members_batch` -- multi-member gzip files (packed archives of gzip streams, BGZF,
+  concatenated .gz files) inflated member by member in parallel (``InflatePlan(..., members=True)``);
 * :func:`build_indexes`, :func:`uncompress_indexed_batch`, :func:`index_info`, :func:`index_range` --
   seek-point indexes: exported once from a chunks plan, then every later decode (or a range out of the
   middle) without the discovery;
@@ -40,6 +42,7 @@ from .api import (  # noqa: F401
     compress_batch, compress_sections_batch, compress_sections_device, compress_sections_last_rings, uncompress_batch, uncompress_sections_batch,
     uncompress_chunks_batch, uncompress_resync_batch, DeflatePlan, InflatePlan,
     uncompress_sizes_batch, uncompress_batch_auto, NO_LIMIT, uncompress_check_batch,
+    uncompress_members_batch, MEMBERS_SIZE_ONLY,
     uncompress_indexed_batch, build_indexes, index_info, index_range, compress_batch_indexed,
     compress_batch_verified, VERIFY_OK, VERIFY_SKIPPED, VERIFY_HEADER, VERIFY_BLOCK_HDR, VERIFY_CODES, VERIFY_LITERAL,
     VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH, VERIFY_BIT_END, VERIFY_TRAILER,

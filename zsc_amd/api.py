@@ -115,6 +115,9 @@ def _load() -> C.CDLL:
                                                    C.c_uint32]
     L.zsc_hip_uncompress_sizes_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u32p, u32p, i32p, C.c_int32]
     L.zsc_hip_inflate_plan_create_check.argtypes = L.zsc_hip_inflate_plan_create_size.argtypes
+    L.zsc_hip_inflate_plan_create_members.argtypes = L.zsc_hip_inflate_plan_create_sections.argtypes + [C.c_uint32]
+    L.zsc_hip_inflate_plan_members.argtypes = [C.c_void_p, u32p, u32p]
+    L.zsc_hip_uncompress_members_batch.argtypes = L.zsc_hip_uncompress_batch.argtypes + [u32p]
     L.zsc_hip_inflate_plan_check_values.argtypes = [C.c_void_p, u32p]
     L.zsc_hip_uncompress_check_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u32p, u32p, i32p, u32p,
                                                  C.c_int32]
@@ -442,6 +445,46 @@ def uncompress_sizes_batch(sources: Sequence[bytes], limits: Sequence[int] | Non
     return rc, list(dlen) if rc == Z_OK else [], list(slen), list(stat)
 
 
+MEMBERS_SIZE_ONLY = 1
+GZIP_WBITS = 31
+
+
+def uncompress_members_batch(sources: Sequence[bytes], dest_caps: Sequence[int] | None, window_bits: int = GZIP_WBITS,
+                             size_only: bool = False):
+    """zsc_hip_uncompress_members_batch: every source is a multi-member gzip file (a packed archive of gzip
+    streams, BGZF, `cat a.gz b.gz`), inflated member by member in parallel.  The result of a file is that of
+    walking it with uncompress_batch, one member after the other in what is left of dest_caps[i], up to the
+    first member that is not Z_OK or to where no 1f 8b follows.  Returns (rc, outputs, consumed, statuses,
+    members).  size_only=True writes nothing (a members plan in size-only mode: dest_caps are limits, None:
+    no limit; the CRC-32 is not compared) and returns the sizes in place of the outputs."""
+    count = len(sources)
+    if size_only:
+        plan = InflatePlan([len(s) for s in sources], dest_caps, window_bits=window_bits, members=True, size_only=True)
+        try:
+            import torch
+            image = bytearray(plan.src_bytes)
+            for s, o in zip(sources, plan.src_offsets):
+                image[o:o + len(s)] = s
+            d_src = torch.frombuffer(image, dtype=torch.uint8).cuda()
+            plan.run(d_src.data_ptr())
+            sizes, used, stat, _ = plan.results()
+            return Z_OK, sizes, used, stat, plan.members()[0]
+        finally:
+            plan.close()
+    if dest_caps is None:
+        raise ValueError("dest_caps are needed")
+    srcs = (C.c_char_p * count)(*sources)
+    slen = (C.c_uint32 * count)(*[len(s) for s in sources])
+    bufs = [C.create_string_buffer(max(c, 1)) for c in dest_caps]
+    dsts = (C.c_void_p * count)(*[C.addressof(b) for b in bufs])
+    dlen = (C.c_uint32 * count)(*dest_caps)
+    stat = (C.c_int32 * count)()
+    memb = (C.c_uint32 * max(count, 1))()
+    rc = lib.zsc_hip_uncompress_members_batch(count, srcs, slen, dsts, dlen, stat, window_bits, memb)
+    outs = [bufs[i].raw[:dlen[i]] for i in range(count)] if rc == Z_OK else []
+    return rc, outs, list(slen), list(stat), list(memb)[:count]
+
+
 def uncompress_check_batch(sources: Sequence[bytes], limits: Sequence[int] | None = None,
                            window_bits: int = DEF_WBITS) -> Tuple[int, List[int], List[int], List[int], List[int]]:
     """zsc_hip_uncompress_check_batch: is every stream intact?  Found on the device without writing any
@@ -724,7 +767,12 @@ class InflatePlan(_Packing):
     chunk_bytes is sized in parallel pieces (chunk_bytes 0 = the default, NO_LIMIT = never cut a stream).
     check_only=True makes a check plan (zsc_hip_inflate_plan_create_check) with the same arguments: the
     streams are decoded into 64 KiB rings, so the check value of the trailer is compared as well -- results()
-    is a plain plan's at dest_caps = limits -- and check_values() hands out the values computed."""
+    is a plain plan's at dest_caps = limits -- and check_values() hands out the values computed.
+    members=True makes a members plan (zsc_hip_inflate_plan_create_members): every item is a multi-member gzip
+    file, inflated member by member in parallel (window_bits must select the gzip wrapper, 24..31); members()
+    gives the member counts and sections() the members the parallel path decoded.  It may be combined with
+    size_only=True (nothing written, dest_caps are limits or None, the CRC-32 is not compared) and with nothing
+    else."""
     _pack_kind = "inflate"
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int] | None,
@@ -733,8 +781,15 @@ class InflatePlan(_Packing):
                  keep_index: bool = False, indexes: Sequence[Optional[bytes]] | None = None,
                  ranges: Sequence[Optional[Tuple[int, int]]] | None = None,
                  src_offsets: Sequence[int] | None = None, size_only: bool = False,
-                 check_only: bool = False):
+                 check_only: bool = False, members: bool = False):
         self.count = n = len(source_lens)
+        if members and (check_only or sections or chunks or resync or keep_index or indexes is not None or
+                        decode_order is not None or chunk_bytes):
+            raise ValueError("a members plan may be size-only and is no other kind of plan")
+        members_size_only = members and size_only
+        if members_size_only and dest_caps is None:
+            dest_caps = [NO_LIMIT] * n
+        size_only = size_only and not members
         if size_only and check_only:
             raise ValueError("a plan is a size plan or a check plan, not both")
         size_only = size_only or check_only  # (a check plan is laid out as a size plan)
@@ -756,7 +811,7 @@ class InflatePlan(_Packing):
             so.append(sb)
             do.append(db)
             sb += (sl + 64 + 15) & ~15
-            db += 0 if size_only else (dc + 64 + 15) & ~15
+            db += 0 if size_only or members_size_only else (dc + 64 + 15) & ~15
         if src_offsets is not None:
             if len(src_offsets) != n:
                 raise ValueError("one source offset per stream")
@@ -769,7 +824,12 @@ class InflatePlan(_Packing):
             raise ValueError("a resync plan is a sections plan, not a chunks plan")
         if sections and chunks:
             raise ValueError("a plan is a sections plan or a chunks plan, not both")
-        if size_only:
+        if members:
+            rc = lib.zsc_hip_inflate_plan_create_members(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens),
+                                                         (C.c_uint64 * n)(*so), (C.c_uint32 * n)(*dest_caps),
+                                                         (C.c_uint64 * n)(*do), window_bits,
+                                                         MEMBERS_SIZE_ONLY if members_size_only else 0)
+        elif size_only:
             create = lib.zsc_hip_inflate_plan_create_check if check_only else lib.zsc_hip_inflate_plan_create_size
             rc = create(C.byref(self._h), n, (C.c_uint32 * n)(*source_lens), (C.c_uint64 * n)(*so),
                         (C.c_uint32 * n)(*dest_caps), window_bits, chunk_bytes)
@@ -847,6 +907,16 @@ class InflatePlan(_Packing):
         if rc != Z_OK:
             raise RuntimeError(f"zsc_hip_inflate_plan_sections failed: {rc}")
         return list(out)[:n]
+
+    def members(self) -> Tuple[List[int], List[int]]:
+        """After results() of a members plan: per file, the members of the walk that were Z_OK, and how many
+        members of the verified prefix (sections()) were claimed by their headers."""
+        n = self.count
+        memb, claimed = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        rc = lib.zsc_hip_inflate_plan_members(self._h, memb, claimed)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_members failed: {rc}")
+        return list(memb)[:n], list(claimed)[:n]
 
     def data_errors(self) -> List[int]:
         """After results(), for every plan kind: per stream, the data errors zsc_uncompress's loop counts

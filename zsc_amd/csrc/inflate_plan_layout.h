@@ -1,6 +1,6 @@
 /*
  * inflate_plan_layout.h -- the host side of the inflate plans that cut streams: how a batch is cut into
- * tiles (sections, resync) or chunks (chunks, size, check), and the device views (IsecPlan, IchkPlan) over
+ * tiles (sections, resync, members) or chunks (chunks, size, check), and the device views (IsecPlan, IchkPlan, MemPlan) over
  * a set of buffers.  Host only: no device code and no HIP call, so the runtime (zsc_hip_runtime.hip) and
  * the lane-emulation harnesses (tests/emu_*) run the same code -- the runtime over its device buffers, a
  * harness with count == 1 over vectors of the exact sizes.
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "inflate_chunks.h"
+#include "inflate_members.h"
 
 /* what the host builds before anything is allocated */
 struct InfLayout {
@@ -44,6 +45,26 @@ inline void sec_layout(uint32_t count, const uint32_t *source_lens, const uint64
         total_in += source_lens[i];
     }
     L.pool = std::min<uint64_t>(SEC_POOL_SLOTS(total_in), 0x0ffffff0u);
+}
+
+/* a members plan: the sections layout over files, with a candidate cap no file of real members reaches (a
+ * member has 20 bytes or more).  dst_offsets and dest_caps may be null (size-only: nothing written, no limit). */
+inline void mem_layout(uint32_t count, const uint32_t *source_lens, const uint64_t *src_offsets,
+                       const uint64_t *dst_offsets, const uint32_t *dest_caps, InfLayout &L)
+{
+    std::vector<uint64_t> zero;
+    std::vector<uint32_t> unlimited;
+    if (!dst_offsets) {
+        zero.assign(count, 0);
+        dst_offsets = zero.data();
+    }
+    if (!dest_caps) {
+        unlimited.assign(count, 0xffffffffu);
+        dest_caps = unlimited.data();
+    }
+    sec_layout(count, source_lens, src_offsets, dst_offsets, dest_caps, L);
+    for (IsecItem &it : L.items)
+        it.cap = it.src_len / MEM_CAND_DIV + SEC_CAND_MIN;
 }
 
 /* per stream longer than a chunk of cb bytes that may_cut(i) allows: its chunks; the scan visits every chunk
@@ -107,6 +128,16 @@ inline void sec_plan_view(IsecPlan &P, const InfPlanMem &m, const InfLayout &L, 
     P.window_bits = window_bits;
     P.work_mul = work_mul;
     P.work_add = work_add;
+}
+
+inline void mem_plan_view(MemPlan &M, const InfPlanMem &m, const InfLayout &L, int32_t window_bits, void *mf,
+                          bool size_only, bool claims, uint32_t work_mul = SEC_WORK_MUL,
+                          uint32_t work_add = SEC_WORK_ADD)
+{
+    sec_plan_view(M.sp, m, L, window_bits, work_mul, work_add);
+    M.mf = (MemFile *)mf;
+    M.size_only = size_only;
+    M.claims = claims;
 }
 
 /* (keep_index stays as it is: a run state of chunks plans) */

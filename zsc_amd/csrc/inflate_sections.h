@@ -112,10 +112,19 @@ typedef struct {
 
 /* ---- whole-wave code: scan and setup ---- */
 
+/* what the scan looks for, as template arguments of the scan.  HIT(v, p, n): the four bytes v at position p of
+ * a stream of n bytes are a pattern; the candidate is then p + ADV.  ENLIST_ALL: every stream with a tile joins
+ * the active list (at its first tile), not only those with a pattern. */
+DEV bool sec_hit_flush(uint32_t v, uint32_t p, uint32_t n)
+{
+    return v == 0xffff0000u && p + 4u < n;
+}
+
 /* step 1 for tile t: write = 0 counts the candidates (and enlists the stream), write = 1 stores
  * their positions in order.  Step k of the four reads 16 * WAVE contiguous bytes, 16 per lane (one
  * dwordx4 load), and the dword behind them: a pattern may straddle lanes, steps and tiles. */
-DEV void sec_scan_tile(const IsecPlan &P, const uint8_t *src_all, uint32_t t, int write)
+template <bool (*HIT)(uint32_t, uint32_t, uint32_t), uint32_t ADV, bool ENLIST_ALL>
+DEV void sec_scan_tile_for(const IsecPlan &P, const uint8_t *src_all, uint32_t t, int write)
 {
     const uint32_t s = GUNI(P.tiles[t].stream);
     const uint32_t t0 = GUNI(P.tiles[t].start);
@@ -144,7 +153,7 @@ DEV void sec_scan_tile(const IsecPlan &P, const uint8_t *src_all, uint32_t t, in
                 for (int sh = 0; sh < 4; sh++) {
                     const uint32_t v = sh ? (w[j] >> (8 * sh)) | (w[j + 1] << (32 - 8 * sh)) : w[j];
                     const uint32_t p = a + 4u * (uint32_t)j + (uint32_t)sh;
-                    if (v == 0xffff0000u && p + 4u < n)
+                    if (HIT(v, p, n))
                         m |= 1ull << (16u * k + 4u * (uint32_t)j + (uint32_t)sh);
                 }
             }
@@ -157,6 +166,12 @@ DEV void sec_scan_tile(const IsecPlan &P, const uint8_t *src_all, uint32_t t, in
         ON_LANE0
         {
             P.tile_cnt[t] = total;
+            if constexpr (ENLIST_ALL) {
+                if (total)
+                    SEC_ADD(&P.scount[s], total);
+                if (t0 == 0u)
+                    P.active[SEC_ADD(&P.q[0], 1u)] = s;
+            } else
             if (total && SEC_ADD(&P.scount[s], total) == 0u)
                 P.active[SEC_ADD(&P.q[0], 1u)] = s;
         }
@@ -177,11 +192,16 @@ DEV void sec_scan_tile(const IsecPlan &P, const uint8_t *src_all, uint32_t t, in
             while (m) {
                 const uint32_t b = (uint32_t)CTZ32(m);
                 m &= m - 1u;
-                P.cstart[r++] = t0 + 16u * WAVE * k + 16u * (uint32_t)LANE + b + 4u;
+                P.cstart[r++] = t0 + 16u * WAVE * k + 16u * (uint32_t)LANE + b + ADV;
             }
         }
         at += tot;
     }
+}
+
+DEV void sec_scan_tile(const IsecPlan &P, const uint8_t *src_all, uint32_t t, int write)
+{
+    sec_scan_tile_for<sec_hit_flush, 4u, false>(P, src_all, t, write);
 }
 
 /* step 2 for the a-th stream with candidates */

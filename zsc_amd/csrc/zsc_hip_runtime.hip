@@ -33,6 +33,7 @@
 #include "inflate_index.h"
 #include "inflate_size.h"
 #include "inflate_check.h"
+#include "inflate_members.h"
 #include "deflate_index.h"
 #include "deflate_verify.h"
 #include "pack.h"
@@ -933,6 +934,79 @@ __global__ __launch_bounds__(64) void k_sec_finish(const uint8_t *__restrict__ s
     const uint32_t na = *P.q;
     for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
         sec_finish(P, src, res, resume, a);
+}
+
+/* kernel 12 (inflate_members.h): multi-member gzip files inflated member by member: the sections plan's
+ * k_sec_setup between two scans for member headers, then claims, count, resolve, write, finish and the
+ * serial step, which is the plan's whole-stream decode (k_inflate does not run on a members plan) */
+__global__ __launch_bounds__(64) void k_mem_scan(const uint8_t *__restrict__ src, MemPlan M, int write)
+{
+    for (uint32_t t = blockIdx.x; t < M.sp.ntiles; t += gridDim.x)
+        mem_scan_tile(M, src, t, write);
+}
+
+__global__ __launch_bounds__(64) void k_mem_claims(const uint8_t *__restrict__ src, MemPlan M)
+{
+    const uint32_t na = UNI(*M.sp.q);
+    for (uint32_t a = blockIdx.x; a < na; a += gridDim.x)
+        mem_claims(M, src, a);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_mem_count(
+    const uint8_t *__restrict__ src, MemPlan M)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfResult r[INF_PER_WAVE];
+    __shared__ InfResume rs[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    mem_count_worker(M, src, &lds_all[grp], &r[grp], &rs[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_mem_resolve(MemPlan M)
+{
+    const uint32_t na = *M.sp.q;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
+        mem_resolve(M, a);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_mem_write(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, MemPlan M)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfResult r[INF_PER_WAVE];
+    __shared__ InfResume rs[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    mem_write_worker(M, src, dst, &lds_all[grp], &r[grp], &rs[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_mem_finish(MemPlan M, InfResult *__restrict__ res, InfResume *__restrict__ resume)
+{
+    const uint32_t na = *M.sp.q;
+    for (uint32_t a = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; a < na; a += gridDim.x * INF_PER_WAVE)
+        mem_finish(M, res, resume, a);
+}
+
+/* (the serial step loops over members and over re-entries around the decoder, which costs registers
+ * (inflate.h, at inflate_stream): it is left to the occupancy the compiler finds, not held to k_inflate's) */
+template <bool SIZE>
+__global__ __launch_bounds__(64) void k_mem_serial(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, MemPlan M,
+                                                   InfResult *__restrict__ res, InfResume *__restrict__ resume)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfResult r[INF_PER_WAVE];
+    __shared__ InfResume rs[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    for (uint32_t s = blockIdx.x * INF_PER_WAVE + grp; s < M.sp.count; s += gridDim.x * INF_PER_WAVE)
+        mem_serial<SIZE>(M, src, dst, &lds_all[grp], &r[grp], &rs[grp], res, resume, s);
 }
 
 /* kernel 7 (inflate_chunks.h): any stream inflated in parallel from block starts found by trial, in
@@ -3679,7 +3753,7 @@ static uint32_t inflate_grid(uint32_t count)
 
 #include "inflate_plan_layout.h"
 
-enum InfPlanKind { INF_PLAIN, INF_SECTIONS, INF_RESYNC, INF_CHUNKS, INF_INDEXED, INF_SIZE, INF_CHECK };
+enum InfPlanKind { INF_PLAIN, INF_SECTIONS, INF_RESYNC, INF_CHUNKS, INF_INDEXED, INF_SIZE, INF_CHECK, INF_MEMBERS };
 
 struct zsc_hip_inflate_plan {
     /* a device buffer of the plan: it cannot be declared without joining `owned`, which destroy releases */
@@ -3690,8 +3764,11 @@ struct zsc_hip_inflate_plan {
     InfPlanKind kind = INF_PLAIN;
     /* what a kind has, and with it which entry points serve it */
     bool has_sections() const { return kind == INF_SECTIONS || kind == INF_RESYNC; } /* resync: a sections plan with more */
-    bool writes_nothing() const { return kind == INF_SIZE || kind == INF_CHECK; }    /* check: a size plan with more */
-    bool has_chunks() const { return kind == INF_CHUNKS || writes_nothing(); }       /* cp and the chunk records */
+    bool writes_nothing() const /* check: a size plan with more; members: in size-only mode */
+    {
+        return kind == INF_SIZE || kind == INF_CHECK || (kind == INF_MEMBERS && mp.size_only);
+    }
+    bool has_chunks() const { return kind == INF_CHUNKS || kind == INF_SIZE || kind == INF_CHECK; } /* cp and the chunk records */
     bool has_rings() const { return kind == INF_CHECK; }                             /* a ring per lane group, a value per stream */
     bool counts_pieces() const { return kind != INF_PLAIN; } /* every other kind keeps d_nsec, a sections plan's */
     uint32_t count = 0;
@@ -3710,6 +3787,9 @@ struct zsc_hip_inflate_plan {
     /* resync plans (inflate_resync.h; sections plans with these buffers besides) */
     IrsyPlan rp = {};
     Buf d_cerr{owned}, d_chain_fl{owned}, d_rst{owned};
+    /* members plans (inflate_members.h; sections plans' buffers, scanned for another pattern, and this one) */
+    MemPlan mp = {};
+    Buf d_mfiles{owned};
     /* size plans (inflate_size.h; with chunks they use cp and the chunks plan's record buffers, never
      * d_ring, d_win or d_chain_ck) */
     bool size_ran = false;
@@ -3885,6 +3965,56 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_create_sections(zsc_hip_inflate_plan 
     if (!ok || !inflate_layout_upload(pl, L))
         return inflate_plan_fail(plan_out);
     sec_plan_view(pl->sp, pl->mem(), L, window_bits);
+    return Z_OK;
+}
+
+/* a sections plan's buffers over files, the candidate cap of mem_layout, and a MemFile per file */
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_members(zsc_hip_inflate_plan **plan_out, U32 count,
+                                                          const U32 *source_lens, const uint64_t *src_offsets,
+                                                          const U32 *dest_caps, const uint64_t *dst_offsets,
+                                                          I32 window_bits, U32 flags)
+{
+    ZSC_ASSERT(plan_out != Z_NULL);
+    *plan_out = nullptr;
+    const bool size_only = (flags & ZSC_HIP_MEMBERS_SIZE_ONLY) != 0;
+    if (window_bits < 16 + 8 || window_bits > 16 + 15 || (flags & ~(U32)ZSC_HIP_MEMBERS_SIZE_ONLY) ||
+        (!size_only && (dest_caps == Z_NULL || dst_offsets == Z_NULL))) {
+        ZSC_WARN("zsc_hip: a members plan takes window_bits 24..31 (the gzip wrapper) and, unless size-only, destinations.");
+        return Z_STREAM_ERROR;
+    }
+    InfLayout L;
+    mem_layout(count, source_lens, src_offsets, size_only ? Z_NULL : dst_offsets, dest_caps, L);
+    std::vector<uint64_t> doff(count);
+    std::vector<U32> caps(count);
+    for (U32 i = 0; i < count; i++) {
+        doff[i] = L.items[i].dst_off;
+        caps[i] = L.items[i].dst_cap;
+    }
+    ZlibReturn rc = zsc_hip_inflate_plan_create(plan_out, count, source_lens, src_offsets, caps.data(), doff.data(),
+                                                window_bits);
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    zsc_hip_inflate_plan *pl = *plan_out;
+    pl->kind = INF_MEMBERS;
+    if (L.tiles.size() >= 0xffffffffull)
+        return inflate_plan_fail(plan_out);
+    const uint64_t nt = std::max<uint64_t>(1, L.tiles.size()), nc = std::max<uint64_t>(1, count), cand = L.pool;
+    pl->ncand_total = cand;
+    bool ok = pl->scratch(pl->d_sitems, sizeof(IsecItem) * nc) && pl->scratch(pl->d_tiles, sizeof(IsecTile) * nt) &&
+              pl->scratch(pl->d_tile_cnt, 4 * nt) && pl->scratch(pl->d_tile_off, 4 * nt) &&
+              pl->scratch(pl->d_scount, 4 * nc) && pl->scratch(pl->d_nsec, 4 * nc) &&
+              pl->scratch(pl->d_sst, sizeof(IsecStream) * nc) && pl->scratch(pl->d_active, 4 * nc) &&
+              pl->scratch(pl->d_q, 16) && pl->scratch(pl->d_cstart, 4 * cand) && pl->scratch(pl->d_cstop, 4 * cand) &&
+              pl->scratch(pl->d_clink, 4 * cand) && pl->scratch(pl->d_clen, 4 * cand) &&
+              pl->scratch(pl->d_chain_k, 4 * cand) && pl->scratch(pl->d_chain_off, 4 * cand) &&
+              (size_only || pl->scratch(pl->d_chain_ck, 4 * cand)) && pl->scratch(pl->d_mfiles, sizeof(MemFile) * nc);
+    if (!ok || !inflate_layout_upload(pl, L))
+        return inflate_plan_fail(plan_out);
+    bool claims = true;
+    if (const char *e = getenv("ZSC_HIP_MEMBERS_CLAIMS")) /* (a test hook, and the A/B switch of the claims step) */
+        claims = atoi(e) != 0;
+    mem_plan_view(pl->mp, pl->mem(), L, window_bits, pl->d_mfiles.p, size_only, claims);
     return Z_OK;
 }
 
@@ -4237,6 +4367,30 @@ static void sec_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst
     }
 }
 
+/* the launches of a members plan, all of its run: scan, setup, scan again, claims, count, resolve, write (not in
+ * size-only mode), finish and the serial step over the files finish left open */
+static void mem_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
+{
+    const MemPlan &M = pl->mp;
+    const uint8_t *src = (const uint8_t *)d_src;
+    InfResult *res = (InfResult *)pl->d_res.p;
+    InfResume *resume = (InfResume *)pl->d_resume.p;
+    const InfGrid g(pl->count, pl->ncand_total, M.sp.ntiles);
+    hipLaunchKernelGGL(k_mem_scan, dim3(g.scans), dim3(64), 0, st, src, M, 0);
+    hipLaunchKernelGGL(k_sec_setup, dim3(g.per_stream), dim3(64), 0, st, M.sp);
+    hipLaunchKernelGGL(k_mem_scan, dim3(g.scans), dim3(64), 0, st, src, M, 1);
+    hipLaunchKernelGGL(k_mem_claims, dim3(g.per_stream), dim3(64), 0, st, src, M);
+    hipLaunchKernelGGL(k_mem_count, dim3(g.groups), dim3(64), 0, st, src, M);
+    hipLaunchKernelGGL(k_mem_resolve, dim3(g.per_group), dim3(64), 0, st, M);
+    if (!M.size_only)
+        hipLaunchKernelGGL(k_mem_write, dim3(g.groups), dim3(64), 0, st, src, (uint8_t *)d_dst, M);
+    hipLaunchKernelGGL(k_mem_finish, dim3(g.per_group), dim3(64), 0, st, M, res, resume);
+    if (M.size_only)
+        hipLaunchKernelGGL(k_mem_serial<true>, dim3(g.per_group), dim3(64), 0, st, src, (uint8_t *)nullptr, M, res, resume);
+    else
+        hipLaunchKernelGGL(k_mem_serial<false>, dim3(g.per_group), dim3(64), 0, st, src, (uint8_t *)d_dst, M, res, resume);
+}
+
 /* the whole-stream decode of what the launches above left: the first launch of a run, and every relaunch of
  * _results.  A check plan's first launch decodes into the rings; its relaunches are the size decode. */
 static void inflate_launch(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st, bool first)
@@ -4272,9 +4426,11 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
     pl->last_dst = d_dst;
     HIP_TRY(hipMemsetAsync(pl->d_resume.p, 0, sizeof(InfResume) * pl->count, st), return Z_STREAM_ERROR);
     HIP_TRY(hipMemsetAsync(pl->d_pending.p, 0, 8, st), return Z_STREAM_ERROR); /* [0] streams to relaunch, [1] the queue */
-    if (pl->has_sections())
+    if (pl->has_sections() || pl->kind == INF_MEMBERS)
         HIP_TRY(hipMemsetAsync(pl->d_scount.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
-    if (pl->has_sections() || pl->has_chunks()) { /* (an indexed plan sets these up itself) */
+    if (pl->kind == INF_MEMBERS)
+        HIP_TRY(hipMemsetAsync(pl->d_mfiles.p, 0, sizeof(MemFile) * pl->count, st), return Z_STREAM_ERROR);
+    if (pl->has_sections() || pl->has_chunks() || pl->kind == INF_MEMBERS) { /* (an indexed plan sets these up itself) */
         HIP_TRY(hipMemsetAsync(pl->d_nsec.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
         HIP_TRY(hipMemsetAsync(pl->d_q.p, 0, 16, st), return Z_STREAM_ERROR);
     }
@@ -4294,7 +4450,10 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         chk_enqueue(pl, d_src, d_dst, st);
     if (pl->kind == INF_INDEXED && idx_enqueue(pl, d_src, d_dst, st) != Z_OK)
         return Z_STREAM_ERROR;
-    inflate_launch(pl, d_src, d_dst, st, true);
+    if (pl->kind == INF_MEMBERS)
+        mem_enqueue(pl, d_src, d_dst, st); /* (its serial step is its whole-stream decode: nothing is relaunched) */
+    else
+        inflate_launch(pl, d_src, d_dst, st, true);
     (void)hipEventRecord(pl->ev1, st);
     pl->timed = true;
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
@@ -4372,6 +4531,27 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U3
     }
     HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
     HIP_TRY(hipMemcpy(sections, pl->d_nsec.p, 4ull * pl->count, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_members(zsc_hip_inflate_plan *pl, U32 *members, U32 *claimed)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (pl->kind != INF_MEMBERS)
+        return Z_STREAM_ERROR;
+    std::vector<MemFile> mf(pl->count, MemFile{0, 0, 0, 0});
+    if ((pl->last_dst || pl->size_ran) && pl->count) {
+        HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+        HIP_TRY(hipMemcpy(mf.data(), pl->d_mfiles.p, sizeof(MemFile) * pl->count, hipMemcpyDeviceToHost),
+                return Z_STREAM_ERROR);
+    }
+    for (uint32_t i = 0; i < pl->count; i++) {
+        if (members)
+            members[i] = mf[i].members;
+        if (claimed)
+            claimed[i] = mf[i].claimed;
+    }
     return Z_OK;
 }
 
@@ -4554,10 +4734,12 @@ extern "C" uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_pla
 
 /* host-pointer batch: lay the streams out one behind the other, make the plan (create(&plan, source offsets,
  * destination offsets)), stage the sources through one device buffer, run, fetch the results, copy the
- * outputs back (dests; null for a plan that writes nothing) and, of a check plan, the values; tear down */
+ * outputs back (dests; null for a plan that writes nothing) and, of a check plan, the values, of a members plan
+ * the member counts if asked for; tear down */
 template <class Create>
 static ZlibReturn uncompress_batch_host(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
-                                        U32 *dest_lens, I32 *statuses, U32 *check_values, Create create)
+                                        U32 *dest_lens, I32 *statuses, U32 *check_values, Create create,
+                                        U32 *members = Z_NULL)
 {
     DeviceScope scope;
     ZSC_ASSERT(sources != Z_NULL);
@@ -4596,6 +4778,8 @@ static ZlibReturn uncompress_batch_host(U32 count, const U8 *const *sources, U32
         rc = zsc_hip_inflate_plan_results(pl, outl.data(), used.data(), stat.data(), nullptr);
     if (rc == Z_OK && pl->has_rings())
         rc = zsc_hip_inflate_plan_check_values(pl, vals.data());
+    if (rc == Z_OK && members)
+        rc = zsc_hip_inflate_plan_members(pl, members, Z_NULL);
     for (U32 i = 0; i < count && rc == Z_OK; i++) {
         if (dests) {
             ZSC_ASSERT(dests[i] != Z_NULL);
@@ -4684,6 +4868,20 @@ extern "C" ZlibReturn zsc_hip_uncompress_sizes_batch(U32 count, const U8 *const 
                                      return zsc_hip_inflate_plan_create_size(pl, count, source_lens, so, dest_lens,
                                                                              window_bits, 0);
                                  });
+}
+
+/* host-pointer batch through a members plan: every source a multi-member gzip file */
+extern "C" ZlibReturn zsc_hip_uncompress_members_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                                       U8 *const *dests, U32 *dest_lens, I32 *statuses,
+                                                       I32 window_bits, U32 *members)
+{
+    ZSC_ASSERT(dests != Z_NULL);
+    return uncompress_batch_host(
+        count, sources, source_lens, dests, dest_lens, statuses, Z_NULL,
+        [&](zsc_hip_inflate_plan **pl, const uint64_t *so, const uint64_t *dof) {
+            return zsc_hip_inflate_plan_create_members(pl, count, source_lens, so, dest_lens, dof, window_bits, 0);
+        },
+        members);
 }
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_check_values(zsc_hip_inflate_plan *pl, U32 *values)
