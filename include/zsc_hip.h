@@ -96,6 +96,23 @@ ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources, U32 *so
 
 /* device-resident plans --------------------------------------------------- */
 
+/* What a run reads, writes and remembers -- for every plan below, deflate and inflate, of every kind,
+ * and for zsc_hip_compress_sections_device:
+ *   reads     the bytes of the items, [offset, + length) each, and behind an item at the most 64 bytes
+ *             (which is why 64 readable bytes must follow the last item of an input).  What those bytes
+ *             hold has no influence on any result: a stream that ends at source_lens[i] has ended there,
+ *             whatever lies behind it -- its own continuation, the next item, 0xFF -- and a buffer is
+ *             compressed as if nothing lay before or behind it.
+ *   writes    nothing outside the slots [offset, + capacity) of the output.  Inside a slot the bytes
+ *             behind the reported length are undefined (a parallel path and its serial fallback may both
+ *             have written there); the bytes behind the capacity are never written, not even the rest of
+ *             the 32-bit word the capacity ends in.  The output need not be cleared before a run.
+ *   remembers nothing: a plan can be run many times, on the same input or on another of the same shape,
+ *             and every run gives what a freshly created plan gives.  What the accessors report
+ *             (sections, members, data errors, check values, indexes) is the last run's.
+ * tests/test_gpu_inflate_surroundings.py, test_gpu_deflate_surroundings.py and test_gpu_plan_rerun.py
+ * hold the plans to it. */
+
 /* A plan fixes the shape of a batch (how many buffers, how long each one is, the
  * codec parameters), owns all scratch memory in HBM and can be run many times on
  * inputs that already live in device memory.  Layout of the device buffers:

@@ -293,6 +293,19 @@ DEV void emit_block(const uint8_t *in, const uint32_t *syms, const ZdBlockRec *r
     be_flush(lds, st, 1);
 }
 
+/* clear word `wi` of a stream for the emit kernel's ORs: whole where it lies below out_cap, byte by byte
+ * where the capacity ends inside it (the bytes behind out_cap are not the stream's to write) */
+DEV void be_zero_word(uint8_t *out, uint32_t wi, uint32_t out_cap)
+{
+    const uint32_t at = wi << 2;
+    if (at + 4u <= out_cap) {
+        ((uint32_t *)out)[wi] = 0;
+        return;
+    }
+    for (uint32_t b = at; b < out_cap; b++)
+        out[b] = 0;
+}
+
 /* one thread per buffer */
 DEV void layout_buffer(const ZdBuf *buf, const ZdParseOut *po, const ZdBlockRec *recs,
                        ZdBlockPlan *plans, ZdResult *res, uint8_t *out)
@@ -322,18 +335,13 @@ DEV void layout_buffer(const ZdBuf *buf, const ZdParseOut *po, const ZdBlockRec 
         return;
     }
     res->status = 0;
-    uint32_t *w = (uint32_t *)out;
-    const uint32_t cap_words = (buf->out_cap + 3u) >> 2;
     for (uint32_t i = 0; i < po->nblocks; i++) {
         const uint32_t first = plans[i].bit_off >> 5;
         for (uint32_t k = 0; k < BE_ZONE_WORDS; k++)
-            if (first + k < cap_words)
-                w[first + k] = 0;
+            be_zero_word(out, first + k, buf->out_cap);
         const uint32_t endw = be_block_end_bit(&recs[i], &plans[i]) >> 5;
-        if (endw < cap_words)
-            w[endw] = 0;
-        if (endw + 1 < cap_words)
-            w[endw + 1] = 0; /* byte padding after the last block can spill one word */
+        be_zero_word(out, endw, buf->out_cap);
+        be_zero_word(out, endw + 1, buf->out_cap); /* byte padding after the last block can spill one word */
     }
     if (buf->wrap == 1) {
         /* reference src/deflate.c:1031-1049 */
