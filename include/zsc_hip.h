@@ -751,6 +751,49 @@ ZlibReturn zsc_hip_uncompress_batch_packed(U32 count, const U8 *sources, const u
                                            uint64_t dest_cap, uint64_t *dest_offsets, U32 *dest_lens,
                                            U32 *consumed, I32 *statuses, I32 window_bits, U32 align);
 
+/* preset dictionaries (decompression only) ---------------------------------
+ *
+ * zsc_hip_inflate_plan_dict_enable gives every stream of a PLAIN plan (zsc_hip_inflate_plan_create,
+ * _create_ordered) one of ndicts dictionaries or none: stream_dict[i] is an index or ZSC_HIP_NO_DICT, and
+ * stream_dict == NULL means dictionary 0 for every stream.  A run then reports what a caller of the
+ * reference gets who answers Z_NEED_DICT with inflateSetDictionary inside zsc_uncompress's loop
+ * (reference src/inflate.c:1446-1486, the DICTID / DICT states :955-968; zsc_amd/csrc/inflate.h, InfDict):
+ *   - a raw plan (window_bits -9 .. -15) applies the stream's dictionary from the start; a zlib-wrapped
+ *     stream (a zlib plan, or the zlib case of an auto-detecting one) only if its header sets FDICT.  A zlib
+ *     stream without FDICT and a gzip member ignore it: a distance past the start of their output is the
+ *     data error it always was;
+ *   - the four big-endian bytes behind a zlib header with FDICT are compared with the Adler-32 of the WHOLE
+ *     dictionary as given.  FDICT with ZSC_HIP_NO_DICT is the plain plan's answer, Z_NEED_DICT with 0 bytes
+ *     out and 0 consumed; another id is Z_DATA_ERROR, 0 bytes out, 0 consumed, nothing resynchronised.  The
+ *     trailer's Adler-32 covers the output alone;
+ *   - with wsize = 1 << window bits (the plan's, or the header's where the plan's are 0) and
+ *     have = min(dict_len, wsize), the stream decodes as if the last `have` bytes of the dictionary lay
+ *     directly before byte 0 of its output: a distance is valid up to pos + have (and, as ever, up to the
+ *     limit the header sets, 32 768 for raw), one more is the plain decoder's "too far back", with its
+ *     resynchronisation;
+ *   - after a data error nothing before the point of resynchronisation can be reached (inflateSync ends in
+ *     inflateReset, :1593-1602), the dictionary included;
+ *   - consumed counts the bytes of the source really used, the two header bytes and the four of the id
+ *     included.  (The one departure: the reference's total_in would miss those six, but it has no one-shot
+ *     call with a dictionary to be equal to, and consumed is how a caller finds a stream's end.)
+ * The dictionaries are host memory of any length; the last 32 KiB of each go to the device once, and the
+ * ids are taken over the whole of each there.  Calling it again replaces the set.  Z_STREAM_ERROR, with the
+ * plan left as it was: an index >= ndicts, and every plan kind but the plain one (_create_sections, _chunks,
+ * _resync, _indexed, _members, _size, _check).  zsc_hip_inflate_plan_pack_enable and runs with other device
+ * buffers work as on any plain plan.  A plan that never enabled dictionaries launches exactly what it
+ * launched before there were any.  zsc_hip_inflate_plan_scratch_bytes counts 32 KiB per dictionary, 8 bytes
+ * per dictionary and 4 bytes per stream.
+ * zsc_hip_inflate_plan_dict_ids: ids[d] = the Adler-32 of dictionary d (Z_STREAM_ERROR on a plan without).
+ * zsc_hip_uncompress_dict_batch: zsc_hip_uncompress_batch through such a plan. */
+#define ZSC_HIP_NO_DICT 0xffffffffu
+
+ZlibReturn zsc_hip_inflate_plan_dict_enable(zsc_hip_inflate_plan *plan, U32 ndicts, const U8 *const *dicts,
+                                            const U32 *dict_lens, const U32 *stream_dict);
+ZlibReturn zsc_hip_inflate_plan_dict_ids(zsc_hip_inflate_plan *plan, U32 *ids);
+ZlibReturn zsc_hip_uncompress_dict_batch(U32 count, const U8 *const *sources, U32 *source_lens, U8 *const *dests,
+                                         U32 *dest_lens, I32 *statuses, I32 window_bits, U32 ndicts,
+                                         const U8 *const *dicts, const U32 *dict_lens, const U32 *stream_dict);
+
 #ifdef __cplusplus
 }
 #endif

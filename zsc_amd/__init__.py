@@ -18,6 +18,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
   every stream, found on the device without writing any output (``InflatePlan(..., check_only=True)``);
 * :func:`uncompress_members_batch` -- multi-member gzip files (packed archives of gzip streams, BGZF,
   concatenated .gz files) inflated member by member in parallel (``InflatePlan(..., members=True)``);
+* :func:`uncompress_dict_batch` -- streams that use zlib preset dictionaries, each with one of a set of
+  shared dictionaries or none (``InflatePlan(..., dicts=[...], stream_dict=[...])``); decompression only;
 * :func:`build_indexes`, :func:`uncompress_indexed_batch`, :func:`index_info`, :func:`index_range` --
   seek-point indexes: exported once from a chunks plan, then every later decode (or a range out of the
   middle) without the discovery;
@@ -43,6 +45,7 @@ from .api import (  # noqa: F401
     uncompress_chunks_batch, uncompress_resync_batch, DeflatePlan, InflatePlan,
     uncompress_sizes_batch, uncompress_batch_auto, NO_LIMIT, uncompress_check_batch,
     uncompress_members_batch, MEMBERS_SIZE_ONLY,
+    uncompress_dict_batch, NO_DICT,
     uncompress_indexed_batch, build_indexes, index_info, index_range, compress_batch_indexed,
     compress_batch_verified, VERIFY_OK, VERIFY_SKIPPED, VERIFY_HEADER, VERIFY_BLOCK_HDR, VERIFY_CODES, VERIFY_LITERAL,
     VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH, VERIFY_BIT_END, VERIFY_TRAILER,

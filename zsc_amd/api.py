@@ -125,6 +125,11 @@ def _load() -> C.CDLL:
     L.zsc_hip_index_info.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(IndexHeader)]
     L.zsc_hip_index_range.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, u32p, u32p, u32p, u32p]
     L.zsc_hip_inflate_plan_index_enable.argtypes = [C.c_void_p, C.c_int32]
+    L.zsc_hip_inflate_plan_dict_enable.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.zsc_hip_inflate_plan_dict_ids.argtypes = [C.c_void_p, C.c_void_p]
+    L.zsc_hip_uncompress_dict_batch.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
     L.zsc_hip_inflate_plan_index_size.argtypes = [C.c_void_p, C.c_uint32, u64p]
     L.zsc_hip_inflate_plan_index_export.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, u64p]
     L.zsc_hip_inflate_plan_create_indexed.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, u32p, u64p, u32p, u64p,
@@ -427,6 +432,7 @@ def uncompress_resync_batch(sources: Sequence[bytes], dest_caps: Sequence[int],
 
 
 NO_LIMIT = 0xFFFFFFFF
+NO_DICT = 0xFFFFFFFF  # ZSC_HIP_NO_DICT: a stream of a plan with preset dictionaries that has none
 
 
 def uncompress_sizes_batch(sources: Sequence[bytes], limits: Sequence[int] | None = None,
@@ -748,6 +754,31 @@ def _uncompress_batch(fn, sources, dest_caps, window_bits):
     return rc, outs, list(slen), list(stat)
 
 
+def _dict_arrays(dicts):
+    """(pointers, lengths) of a list of dictionaries for the C ABI; the pointers keep the bytes alive"""
+    n = len(dicts)
+    keep = [bytes(d) for d in dicts]
+    ptrs = (C.c_char_p * max(n, 1))(*keep)
+    ptrs._keep = keep
+    return ptrs, (C.c_uint32 * max(n, 1))(*[len(d) for d in keep])
+
+
+def uncompress_dict_batch(sources: Sequence[bytes], dest_caps: Sequence[int], dicts: Sequence[bytes],
+                          stream_dict: Sequence[int] | None = None, window_bits: int = DEF_WBITS):
+    """uncompress_batch for streams that use zlib preset dictionaries (zsc_hip_uncompress_dict_batch):
+    stream_dict[i] is the index of stream i's dictionary in dicts or NO_DICT; None: dictionary 0 for all.
+    -> (rc, outputs, consumed, statuses)."""
+    if stream_dict is not None and len(stream_dict) != len(sources):
+        raise ValueError("one dictionary index per stream")
+    ptrs, lens = _dict_arrays(dicts)
+    sd = None if stream_dict is None else (C.c_uint32 * max(len(sources), 1))(*stream_dict)
+
+    def fn(count, srcs, slen, dsts, dlen, stat, wbits):
+        return lib.zsc_hip_uncompress_dict_batch(count, srcs, slen, dsts, dlen, stat, wbits, len(dicts), ptrs, lens, sd)
+
+    return _uncompress_batch(fn, sources, dest_caps, window_bits)
+
+
 class InflatePlan(_Packing):
     """Device-resident inflate batch (see include/zsc_hip.h).  sections=True makes a sections plan
     (zsc_hip_inflate_plan_create_sections: full-flush sections decoded in parallel; it takes no
@@ -772,7 +803,11 @@ class InflatePlan(_Packing):
     file, inflated member by member in parallel (window_bits must select the gzip wrapper, 24..31); members()
     gives the member counts and sections() the members the parallel path decoded.  It may be combined with
     size_only=True (nothing written, dest_caps are limits or None, the CRC-32 is not compared) and with nothing
-    else."""
+    else.
+    dicts=[bytes, ...] gives the streams of a plain plan zlib preset dictionaries
+    (zsc_hip_inflate_plan_dict_enable): stream_dict[i] is the index of stream i's dictionary or NO_DICT, None
+    means dictionary 0 for every stream.  dict_enable() replaces the set later; dict_ids() hands out the
+    dictionaries' Adler-32 values."""
     _pack_kind = "inflate"
 
     def __init__(self, source_lens: Sequence[int], dest_caps: Sequence[int] | None,
@@ -781,8 +816,11 @@ class InflatePlan(_Packing):
                  keep_index: bool = False, indexes: Sequence[Optional[bytes]] | None = None,
                  ranges: Sequence[Optional[Tuple[int, int]]] | None = None,
                  src_offsets: Sequence[int] | None = None, size_only: bool = False,
-                 check_only: bool = False, members: bool = False):
+                 check_only: bool = False, members: bool = False, dicts: Sequence[bytes] | None = None,
+                 stream_dict: Sequence[int] | None = None):
         self.count = n = len(source_lens)
+        if stream_dict is not None and dicts is None:
+            raise ValueError("stream_dict needs dicts")
         if members and (check_only or sections or chunks or resync or keep_index or indexes is not None or
                         decode_order is not None or chunk_bytes):
             raise ValueError("a members plan may be size-only and is no other kind of plan")
@@ -867,6 +905,35 @@ class InflatePlan(_Packing):
             raise RuntimeError(f"zsc_hip_inflate_plan_create failed: {rc}")
         if keep_index and lib.zsc_hip_inflate_plan_index_enable(self._h, 1) != Z_OK:
             raise RuntimeError("zsc_hip_inflate_plan_index_enable failed")
+        if dicts is not None:
+            rc = self.dict_enable(dicts, stream_dict)
+            if rc != Z_OK:
+                self.close()
+                raise ValueError(f"zsc_hip_inflate_plan_dict_enable failed: {rc}")
+
+    def dict_enable(self, dicts: Sequence[bytes], stream_dict: Sequence[int] | None = None) -> int:
+        """Gives the streams these preset dictionaries (replacing the ones the plan had).  Returns the
+        ZlibReturn: Z_STREAM_ERROR, with the plan as it was, for an index out of range and for every plan kind
+        but the plain one."""
+        if stream_dict is not None and len(stream_dict) != self.count:
+            raise ValueError("one dictionary index per stream")
+        ptrs, lens = _dict_arrays(dicts)
+        sd = None if stream_dict is None else (C.c_uint32 * max(self.count, 1))(*stream_dict)
+        rc = lib.zsc_hip_inflate_plan_dict_enable(self._h, len(dicts), ptrs, lens, sd)
+        if rc == Z_OK:
+            self._ndicts = len(dicts)
+        return rc
+
+    def dict_ids(self) -> List[int]:
+        """The Adler-32 of each of the plan's dictionaries, taken over the whole of it."""
+        n = getattr(self, "_ndicts", None)
+        if n is None:
+            raise ValueError("the plan has no dictionaries")
+        out = (C.c_uint32 * max(n, 1))()
+        rc = lib.zsc_hip_inflate_plan_dict_ids(self._h, out)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_dict_ids failed: {rc}")
+        return list(out)[:n]
 
     def export_index(self, i: int) -> Optional[bytes]:
         """After results() of a chunks plan made with keep_index: the seek-point index of stream i, or

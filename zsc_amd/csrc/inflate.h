@@ -310,6 +310,10 @@ DEV uint32_t inf_sync_search(const uint8_t *src, uint32_t n, uint64_t sy_start, 
  *                    the whole stream as SEC = 0 decodes it (results to res / rs); with INF_SEC_BITSTART |
  *                    INF_SEC_EXTWIN | INF_SEC_NOTRAIL it is the write pass of a chained piece. */
 #define INF_SEC_RING 256u
+/* the dictionary variant, with dc pointing to an InfDict:
+ *   INF_SEC_DICT     the whole stream as SEC = 0 decodes it (results to res / rs), with a preset dictionary as the
+ *                    history before byte 0 of the output (see InfDict) */
+#define INF_SEC_DICT 512u
 #define INF_WIN 32768u   /* window entries: win[INF_WIN - d] is the byte d before the piece */
 #define INF_PH 0x8000u   /* a placeholder symbol of the 16-bit output */
 #define INF_PC_CANDS 4u  /* candidates per chunk */
@@ -354,6 +358,31 @@ typedef struct {
     uint64_t end_bit;     /* stream bit offset where the piece stopped */
 } InfPiece;
 
+/* INF_SEC_DICT: the stream's preset dictionary, as a caller of the reference would hand it over by answering
+ * Z_NEED_DICT with inflateSetDictionary (reference src/inflate.c:1446-1486; the DICTID and DICT states
+ * :955-968) inside zsc_uncompress's loop.
+ *   - A raw stream has it from the start (wrap == 0, :1458); a zlib stream only if its header sets FDICT, and
+ *     then only if the four big-endian bytes behind the header are the Adler-32 of the whole dictionary (id;
+ *     :1462-1467).  Another id is Z_DATA_ERROR with nothing decoded, nothing consumed and no
+ *     resynchronisation; no dictionary at all (win == null) is the plain decoder's Z_NEED_DICT.  A zlib stream
+ *     without FDICT and a gzip member never look at it.
+ *   - updatewindow (:1472) leaves the last have = min(len, 1 << wbits) bytes in the window: they lie directly
+ *     before byte 0, win[INF_WIN - d] being the byte d before it (the INF_SEC_EXTWIN layout, of which the
+ *     last min(len, INF_WIN) entries are filled).  A distance is valid up to pos + have and, as ever, up to
+ *     dmax, which the dictionary does not change.
+ *   - The check value of the output starts afresh (:965): the dictionary's bytes are not part of it.
+ *   - Only the first inflate() call has it: inflateSync ends in inflateReset (:1593-1602), which drops the
+ *     window, so the resumed entry (rs->state == 1) reaches nothing before out_base, as in the plain decoder.
+ * The one deliberate departure: `consumed` counts the bytes of the source really used, the two header bytes
+ * and the four of the id included.  The reference's total_in would miss them ("RESTORE(); return Z_NEED_DICT"
+ * skips the exit bookkeeping, :966-967), but it has no one-shot call with a dictionary to be equal to, and
+ * consumed is how a caller finds the end of a stream inside a larger buffer. */
+typedef struct {
+    const uint8_t *win; /* null: the stream has no dictionary */
+    uint32_t len;       /* the whole dictionary's length */
+    uint32_t id;        /* the whole dictionary's Adler-32 */
+} InfDict;
+
 /* the whole stream; mirrors zsc_uncompress_gzip2 with gz_head == NULL */
 /* One inflate() call of zsc_uncompress's loop (reference src/zsc_uncompr.c:104-125): decodes
  * until the stream ends or fails.  Returns 1 after a data error: *rs then holds what
@@ -364,14 +393,17 @@ typedef struct {
  * decode loop, costs it a wave per SIMD; the sound streams would pay for the damaged ones. */
 template <uint32_t SEC = 0u, class CK = void>
 DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume *rs, InfSecInfo *si = nullptr,
-                      InfPiece *pc = nullptr, CK *chk = nullptr)
+                      InfPiece *pc = nullptr, CK *chk = nullptr, const InfDict *dc = nullptr)
 {
     constexpr bool RING = (SEC & INF_SEC_RING) != 0u;
+    constexpr bool DICT = (SEC & INF_SEC_DICT) != 0u;
     constexpr bool PIECE_OUT = (SEC & (INF_SEC_SYM16 | INF_SEC_EXTWIN)) != 0u ||
                                (SEC & (INF_SEC_BITSTART | INF_SEC_COUNT)) == (INF_SEC_BITSTART | INF_SEC_COUNT);
     constexpr bool SIZE_ONLY = (SEC & INF_SEC_SIZE) != 0u;
-    constexpr bool SECTION = (SEC & ~INF_SEC_RING) != 0u && !SIZE_ONLY; /* results go to *si (and *pc) */
+    constexpr bool SECTION = (SEC & ~(INF_SEC_RING | INF_SEC_DICT)) != 0u && !SIZE_ONLY; /* results go to *si (and *pc) */
+    static_assert(!DICT || SEC == INF_SEC_DICT, "the dictionary variant is the plain decoder's only");
     (void)chk;
+    (void)dc;
     const uint8_t *src = job.src;
     const uint32_t n = job.n, cap = job.cap;
     uint8_t *dst = job.dst;
@@ -443,6 +475,13 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
     uint32_t rg_folded = 0;
     (void)rg;
     (void)rg_folded;
+    /* (the dictionary variant only) the window image, the dictionary bytes this inflate() call can reach, and
+     * whether inflateSetDictionary refused the dictionary */
+    const uint8_t *dc_win = nullptr;
+    uint32_t dc_have = 0, dc_refused = 0;
+    (void)dc_win;
+    (void)dc_have;
+    (void)dc_refused;
 
 /* top up the bit buffer to at least 32 bits (or to the end of the input) */
 #define INF_REFILL()                                                                          \
@@ -661,6 +700,14 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
             goto done;
         }
         INF_SEEK(nin + taken);
+    } else if (DICT && !wrap) {
+        if constexpr (DICT) {
+            if (dc->win != nullptr) {
+                const uint32_t dl = GUNI(dc->len);
+                dc_win = dc->win;
+                dc_have = dl < (1u << wb) ? dl : 1u << wb;
+            }
+        }
     } else if (wrap) {
         INF_NEED(16);
         const uint32_t hw = (uint32_t)br.hold & 0xffffu;
@@ -722,8 +769,25 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                 /* preset dictionary: the reference returns Z_NEED_DICT from the DICT state
                  * without its exit bookkeeping, so nothing counts as consumed */
                 INF_NEED(32);
-                rc = INF_NEED_DICT;
-                goto done;
+                if constexpr (DICT) {
+                    if (dc->win != nullptr) {
+                        uint32_t v;
+                        INF_TAKE(v, 32);
+                        v = (v >> 24) | ((v >> 8) & 0xff00u) | ((v & 0xff00u) << 8) | (v << 24);
+                        if (v != GUNI(dc->id)) {
+                            dc_refused = 1;
+                            rc = INF_DATA;
+                            goto done;
+                        }
+                        const uint32_t dl = GUNI(dc->len);
+                        dc_win = dc->win;
+                        dc_have = dl < (1u << wbits_eff) ? dl : 1u << wbits_eff;
+                    }
+                }
+                if (!DICT || dc_win == nullptr) {
+                    rc = INF_NEED_DICT;
+                    goto done;
+                }
             }
         }
     }
@@ -1023,7 +1087,9 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                 xb = dsu < 4 ? 0u : (dsu >> 1) - 1u;
                 const uint32_t dist = (dsu < 4 ? dsu : (2u + (dsu & 1u)) << ((dsu >> 1) - 1u)) + 1u +
                                       ((uint32_t)br.hold & ((1u << xb) - 1u));
-                if ((dsu > 29u) | (br.bits < xb) | (dist > dmax) | (pos >= cap) | (!PIECE_OUT && dist > pos - out_base)) {
+                if ((dsu > 29u) | (br.bits < xb) | (dist > dmax) | (pos >= cap) |
+                    (!PIECE_OUT && !DICT && dist > pos - out_base) |
+                    (DICT && dist > pos - out_base && dist - (pos - out_base) > dc_have)) {
                     if (dsu > 29u)
                         INF_BAD;
                     if (br.bits < xb)
@@ -1101,6 +1167,26 @@ DEV int inflate_stream(const InfJob &job, InfLds *lds, InfResult *res, InfResume
                                 const uint32_t q = (uint32_t)(((float)i + 0.5f) * rdist);
                                 const uint32_t s = pos - dist + (i - q * dist);
                                 const uint8_t b = (int32_t)s < 0 ? pc_win[INF_WIN + s]
+                                                  : s + INF_STAGE >= pos + can ? lds->stage[s & (INF_STAGE - 1)]
+                                                                               : dst[s];
+                                lds->stage[(pos + i) & (INF_STAGE - 1)] = b;
+                                dst[pos + i] = b;
+                            }
+                        }
+                        WAVE_SYNC();
+                    }
+                } else if constexpr (DICT) {
+                    /* (as the copy below; a source before byte 0 is a byte of the dictionary.  A source in
+                     * the output is below pos, and one before it wraps to 2^32 - INF_WIN at the least, which
+                     * no pos that a distance can pass comes near) */
+                    for (uint32_t k = 0; k < can; k += GRP) {
+                        FOR_GLANES
+                        {
+                            uint32_t i = k + (uint32_t)GLANE;
+                            if (i < can) {
+                                const uint32_t q = (uint32_t)(((float)i + 0.5f) * rdist);
+                                const uint32_t s = pos - dist + (i - q * dist);
+                                const uint8_t b = s >= pos ? dc_win[INF_WIN + s]
                                                   : s + INF_STAGE >= pos + can ? lds->stage[s & (INF_STAGE - 1)]
                                                                                : dst[s];
                                 lds->stage[(pos + i) & (INF_STAGE - 1)] = b;
@@ -1304,6 +1390,10 @@ done:
         uint32_t used_bytes = (uint32_t)((BR_USED + 7u) >> 3);
         if (exhausted || used_bytes > n)
             used_bytes = n;
+        if constexpr (DICT) {
+            if (dc_refused)
+                used_bytes = 0; /* (nothing has been decoded: the stream is where Z_NEED_DICT left it) */
+        }
         res->status = rc == INF_END ? 0 : rc;
         res->out_len = rc == INF_NEED_DICT ? 0u : pos;
         res->consumed = rc == INF_NEED_DICT ? 0u : used_bytes;
@@ -1331,6 +1421,18 @@ DEV void inflate_with_resync(const InfJob &job, InfLds *lds, InfResult *res)
     rs.out_pos = rs.errors = rs.gzip = rs.sy_lo = rs.sy_hi = rs.sy_rb = 0;
     for (uint32_t round = 0; round < job.n / 4u + 2u; round++) {
         if (!inflate_stream(job, lds, res, &rs))
+            return;
+    }
+}
+
+/* the same for a stream with a preset dictionary (k_inflate_dict and its relaunches) */
+DEV void inflate_dict_with_resync(const InfJob &job, const InfDict &dc, InfLds *lds, InfResult *res)
+{
+    InfResume rs;
+    rs.state = 0;
+    rs.out_pos = rs.errors = rs.gzip = rs.sy_lo = rs.sy_hi = rs.sy_rb = 0;
+    for (uint32_t round = 0; round < job.n / 4u + 2u; round++) {
+        if (!inflate_stream<INF_SEC_DICT>(job, lds, res, &rs, nullptr, nullptr, (void *)nullptr, &dc))
             return;
     }
 }

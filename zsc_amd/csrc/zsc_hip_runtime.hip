@@ -882,6 +882,74 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU
     }
 }
 
+/* kernel 5d: k_inflate for a plan with preset dictionaries (zsc_hip_inflate_plan_dict_enable): the same queue,
+ * the dictionary variant of the decoder.  A stream's dictionary is one of the plan's window images (imgs,
+ * INF_WIN bytes each: the INF_SEC_EXTWIN layout) or none; the images are shared by all the streams that use
+ * them and stay in L2.  k_inflate itself never sees a dictionary: a plan without them launches it as ever. */
+typedef struct {
+    uint32_t len, id; /* the whole dictionary's length and Adler-32 */
+} ZdInfDict;
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_inflate_dict(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const ZdInfItem *__restrict__ items,
+    const uint32_t *__restrict__ order, InfResult *__restrict__ res, InfResume *__restrict__ resume,
+    uint32_t *__restrict__ pending, int32_t window_bits, uint32_t count, const uint8_t *__restrict__ imgs,
+    const ZdInfDict *__restrict__ dicts, const uint32_t *__restrict__ dict_of)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    InfLds *lds = &lds_all[grp];
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds->cktab = crc_table;
+    for (;;) {
+        uint32_t slot = 0;
+        if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+            slot = atomicAdd(pending + 1, 1u);
+        slot = (uint32_t)__shfl((int)slot, (int)(threadIdx.x & (64u - INF_GROUP)));
+        if (slot >= count)
+            break;
+        const uint32_t i = order[slot];
+        if (resume[i].state == 2u)
+            continue;
+        const ZdInfItem it = items[i];
+        InfJob job;
+        job.src = src + it.src_off;
+        job.n = it.src_len;
+        job.dst = dst + it.dst_off;
+        job.cap = it.dst_cap;
+        job.window_bits = window_bits;
+        const uint32_t d = dict_of[i];
+        InfDict dc = {nullptr, 0u, 0u};
+        if (d != ZSC_HIP_NO_DICT) {
+            dc.win = imgs + (uint64_t)d * INF_WIN;
+            dc.len = dicts[d].len;
+            dc.id = dicts[d].id;
+        }
+        if (inflate_stream<INF_SEC_DICT>(job, lds, &res[i], &resume[i], nullptr, nullptr, (void *)nullptr, &dc)) {
+            if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+                atomicAdd(pending, 1u);
+        }
+    }
+}
+
+/* the plan's dictionaries made ready, one wavefront each: the id is the Adler-32 of the whole dictionary as
+ * given (whole + at[d], 16-byte aligned), the image its last min(len, INF_WIN) bytes, right-aligned */
+__global__ __launch_bounds__(64) void k_dict_setup(const uint8_t *__restrict__ whole, const uint64_t *__restrict__ at,
+                                                   ZdInfDict *__restrict__ dicts, uint8_t *__restrict__ imgs)
+{
+    const uint32_t d = blockIdx.x;
+    const uint8_t *in = whole + at[d];
+    const uint32_t n = dicts[d].len;
+    const uint32_t id = ck_adler32(in, n);
+    if (threadIdx.x == 0)
+        dicts[d].id = id;
+    const uint32_t have = n < INF_WIN ? n : INF_WIN;
+    uint8_t *img = imgs + (uint64_t)d * INF_WIN + (INF_WIN - have);
+    for (uint32_t k = threadIdx.x; k < have; k += 64u)
+        img[k] = in[n - have + k];
+}
+
 /* kernel 6 (inflate_sections.h): the full-flush sections of each stream inflated in parallel, in
  * six launches ahead of k_inflate */
 __global__ __launch_bounds__(64) void k_sec_scan(const uint8_t *__restrict__ src, IsecPlan P, int write)
@@ -3813,6 +3881,12 @@ struct zsc_hip_inflate_plan {
     bool timed = false;
     /* packing (pack.h), off unless zsc_hip_inflate_plan_pack_enable was called */
     PackState pack;
+    /* preset dictionaries, off unless zsc_hip_inflate_plan_dict_enable was called (plain plans only): the window
+     * images, a ZdInfDict per dictionary and every stream's index */
+    bool dict_on = false;
+    uint64_t dict_scratch = 0; /* what of scratch_bytes they hold */
+    std::vector<U32> dict_ids;
+    Buf d_dict_img{owned}, d_dict_tab{owned}, d_dict_of{owned};
 
     /* a buffer beyond a plain plan's: its bytes are the plan's scratch */
     bool scratch(DevBuf &b, uint64_t bytes)
@@ -4407,6 +4481,10 @@ static void inflate_launch(zsc_hip_inflate_plan *pl, const void *d_src, void *d_
     else if (pl->writes_nothing())
         hipLaunchKernelGGL(k_inflate_size, dim3(inflate_grid(pl->count)), dim3(64), 0, st, src, items, order, res,
                            resume, pending, pl->window_bits, pl->count);
+    else if (pl->dict_on)
+        hipLaunchKernelGGL(k_inflate_dict, dim3(inflate_grid(pl->count)), dim3(64), 0, st, src, (uint8_t *)d_dst, items,
+                           order, res, resume, pending, pl->window_bits, pl->count, (const uint8_t *)pl->d_dict_img.p,
+                           (const ZdInfDict *)pl->d_dict_tab.p, (const uint32_t *)pl->d_dict_of.p);
     else
         hipLaunchKernelGGL(k_inflate, dim3(inflate_grid(pl->count)), dim3(64), 0, st, src, (uint8_t *)d_dst, items, order,
                            res, resume, pending, pl->window_bits, pl->count);
@@ -4732,6 +4810,86 @@ extern "C" uint64_t zsc_hip_inflate_plan_scratch_bytes(const zsc_hip_inflate_pla
     return pl ? pl->scratch_bytes : 0;
 }
 
+/* ---- preset dictionaries of a plain inflate plan (inflate.h, InfDict) ---------------------------- */
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_dict_enable(zsc_hip_inflate_plan *pl, U32 ndicts, const U8 *const *dicts,
+                                                       const U32 *dict_lens, const U32 *stream_dict)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    if (pl->kind != INF_PLAIN || (ndicts && (dicts == Z_NULL || dict_lens == Z_NULL)))
+        return Z_STREAM_ERROR;
+    std::vector<U32> of(std::max(1u, pl->count), ZSC_HIP_NO_DICT);
+    for (uint32_t i = 0; i < pl->count; i++) {
+        of[i] = stream_dict ? stream_dict[i] : 0u;
+        if (of[i] != ZSC_HIP_NO_DICT && of[i] >= ndicts)
+            return Z_STREAM_ERROR;
+    }
+    /* the whole dictionaries go up once, for their ids; the plan keeps the images (k_dict_setup) */
+    std::vector<uint64_t> at(std::max(1u, ndicts), 0);
+    std::vector<ZdInfDict> tab(std::max(1u, ndicts), ZdInfDict{0u, 0u});
+    uint64_t total = 0;
+    for (uint32_t d = 0; d < ndicts; d++) {
+        if (dict_lens[d] && dicts[d] == Z_NULL)
+            return Z_STREAM_ERROR;
+        at[d] = total;
+        tab[d].len = dict_lens[d];
+        total += ((uint64_t)dict_lens[d] + 15u) & ~15ull;
+    }
+    DevBuf whole, d_at, img, d_tab, d_of;
+    const uint64_t img_bytes = (uint64_t)INF_WIN * std::max(1u, ndicts);
+    bool ok = whole.ensure(total + 16) && d_at.ensure(8ull * at.size()) && img.ensure(img_bytes) &&
+              d_tab.ensure(sizeof(ZdInfDict) * tab.size()) && d_of.ensure(4ull * of.size());
+    ok = ok && hipMemset(img.p, 0, img_bytes) == hipSuccess &&
+         hipMemcpy(d_at.p, at.data(), 8ull * at.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d_tab.p, tab.data(), sizeof(ZdInfDict) * tab.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d_of.p, of.data(), 4ull * of.size(), hipMemcpyHostToDevice) == hipSuccess;
+    for (uint32_t d = 0; d < ndicts && ok; d++)
+        if (dict_lens[d])
+            ok = hipMemcpy((uint8_t *)whole.p + at[d], dicts[d], dict_lens[d], hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && ndicts) {
+        hipLaunchKernelGGL(k_dict_setup, dim3(ndicts), dim3(64), 0, nullptr, (const uint8_t *)whole.p,
+                           (const uint64_t *)d_at.p, (ZdInfDict *)d_tab.p, (uint8_t *)img.p);
+        ok = hipStreamSynchronize(nullptr) == hipSuccess &&
+             hipMemcpy(tab.data(), d_tab.p, sizeof(ZdInfDict) * ndicts, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    whole.release();
+    d_at.release();
+    if (!ok) {
+        img.release();
+        d_tab.release();
+        d_of.release();
+        return Z_MEM_ERROR;
+    }
+    /* the set the plan had, if any, is replaced (its last run may still be reading it) */
+    (void)hipStreamSynchronize(pl->last_stream);
+    std::swap(static_cast<DevBuf &>(pl->d_dict_img), img);
+    std::swap(static_cast<DevBuf &>(pl->d_dict_tab), d_tab);
+    std::swap(static_cast<DevBuf &>(pl->d_dict_of), d_of);
+    img.release();
+    d_tab.release();
+    d_of.release();
+    pl->scratch_bytes -= pl->dict_scratch;
+    pl->dict_scratch = img_bytes + sizeof(ZdInfDict) * tab.size() + 4ull * of.size();
+    pl->scratch_bytes += pl->dict_scratch;
+    pl->dict_ids.resize(ndicts);
+    for (uint32_t d = 0; d < ndicts; d++)
+        pl->dict_ids[d] = tab[d].id;
+    pl->dict_on = true;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_dict_ids(zsc_hip_inflate_plan *pl, U32 *ids)
+{
+    ZSC_ASSERT(pl != Z_NULL);
+    if (!pl->dict_on)
+        return Z_STREAM_ERROR;
+    ZSC_ASSERT(ids != Z_NULL || pl->dict_ids.empty());
+    for (size_t d = 0; d < pl->dict_ids.size(); d++)
+        ids[d] = pl->dict_ids[d];
+    return Z_OK;
+}
+
 /* host-pointer batch: lay the streams out one behind the other, make the plan (create(&plan, source offsets,
  * destination offsets)), stage the sources through one device buffer, run, fetch the results, copy the
  * outputs back (dests; null for a plan that writes nothing) and, of a check plan, the values, of a members plan
@@ -4857,6 +5015,26 @@ extern "C" ZlibReturn zsc_hip_uncompress_indexed_batch(U32 count, const U8 *cons
 {
     return uncompress_batch_impl(count, sources, source_lens, dests, dest_lens, statuses, window_bits, 4, indexes,
                                  index_lens);
+}
+
+/* host-pointer batch through a plain plan with preset dictionaries */
+extern "C" ZlibReturn zsc_hip_uncompress_dict_batch(U32 count, const U8 *const *sources, U32 *source_lens,
+                                                    U8 *const *dests, U32 *dest_lens, I32 *statuses, I32 window_bits,
+                                                    U32 ndicts, const U8 *const *dicts, const U32 *dict_lens,
+                                                    const U32 *stream_dict)
+{
+    ZSC_ASSERT(dests != Z_NULL);
+    return uncompress_batch_host(
+        count, sources, source_lens, dests, dest_lens, statuses, Z_NULL,
+        [&](zsc_hip_inflate_plan **pl, const uint64_t *so, const uint64_t *dof) {
+            ZlibReturn rc = zsc_hip_inflate_plan_create(pl, count, source_lens, so, dest_lens, dof, window_bits);
+            if (rc == Z_OK) {
+                rc = zsc_hip_inflate_plan_dict_enable(*pl, ndicts, dicts, dict_lens, stream_dict);
+                if (rc != Z_OK)
+                    inflate_plan_fail(pl, rc);
+            }
+            return rc;
+        });
 }
 
 /* host-pointer batch through a size plan (default chunk_bytes): the sources staged in one device buffer */
