@@ -111,7 +111,27 @@ ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources, U32 *so
  *             and every run gives what a freshly created plan gives.  What the accessors report
  *             (sections, members, data errors, check values, indexes) is the last run's.
  * tests/test_gpu_inflate_surroundings.py, test_gpu_deflate_surroundings.py and test_gpu_plan_rerun.py
- * hold the plans to it. */
+ * hold the plans to it.
+ *
+ * Streams -- for the same plans:
+ *   - what _run, _verify and _pack enqueue is ordered after everything enqueued earlier on the stream they
+ *     are given and before everything enqueued later on it, like a kernel launched there: the input may come
+ *     from a copy or a kernel still pending on that stream, and a consumer enqueued behind the call reads the
+ *     finished output.  None of the three waits on the host for device work.
+ *   - a clean batch is complete in stream order at the end of _run.  The inflate plans' resynchronisation of
+ *     damaged streams (relaunches from the flush marker behind a data error) finishes in _results, and only
+ *     for the plan's last run: a run that another _run follows before _results is left where its first pass
+ *     got to.
+ *   - a plan has ONE set of scratch.  A _run enqueued on another stream than the plan's unfinished earlier
+ *     work -- a run, a verification or a pack -- waits for that work on the device (an event behind each
+ *     enqueue, hipStreamWaitEvent only where the streams differ); the host does not wait.  A plan that only
+ *     ever sees one stream enqueues nothing for this but one event record per call.
+ *   - _results, every accessor and _destroy wait, on the host, for all of the plan's work, whatever streams
+ *     it went to: every stream the plan was given since the last such wait is synchronised, so it must still
+ *     exist then.
+ *   - the caller keeps the input unchanged until _results: an inflate plan's relaunches and the index exports
+ *     read it again.
+ * One plan is used from one host thread at a time.  tests/test_gpu_streams.py holds the plans to it. */
 
 /* A plan fixes the shape of a batch (how many buffers, how long each one is, the
  * codec parameters), owns all scratch memory in HBM and can be run many times on

@@ -657,7 +657,8 @@ class _Packing:
     def pack(self, d_output: int, d_packed: int, cap: int, stream: int = 0) -> int:
         """After run() on the same stream, or after results(), any number of times: enqueue the pack of the
         items at d_output (the run's output or a copy of it at the plan's offsets) into the cap bytes at
-        d_packed (16-byte aligned).  Returns the ZlibReturn: Z_STREAM_ERROR on a plan without pack_enable()."""
+        d_packed (16-byte aligned).  Returns the ZlibReturn: Z_STREAM_ERROR on a plan without pack_enable().
+        stream: the pack is ordered in it like a kernel; the plan's next run, results() and close() wait for it."""
         return getattr(lib, f"zsc_hip_{self._pack_kind}_plan_pack")(self._h, C.c_void_p(d_output), C.c_void_p(d_packed),
                                                                      cap, C.c_void_p(stream))
 
@@ -688,7 +689,8 @@ def unpack(d_packed: int, packed_offsets: Sequence[int], lens: Sequence[int], d_
            dst_offsets: Sequence[int], stream: int = 0) -> int:
     """zsc_hip_unpack: item i, lens[i] bytes at packed_offsets[i] of the device image d_packed (ascending, any
     alignment; a count + 1 table as pack_results() returns it will do), to dst_offsets[i] (multiples of 16) of
-    d_dst; no other byte of d_dst is written.  Asynchronous on stream.  Returns the ZlibReturn."""
+    d_dst; no other byte of d_dst is written.  Asynchronous on stream.  Returns the ZlibReturn.
+    stream: the three tables are uploaded before the call returns, the launch is ordered in the stream like a kernel."""
     n = len(lens)
     return lib.zsc_hip_unpack(n, C.c_void_p(d_packed), (C.c_uint64 * n)(*packed_offsets[:n]), (C.c_uint32 * n)(*lens),
                               C.c_void_p(d_dst), (C.c_uint64 * n)(*dst_offsets), C.c_void_p(stream))
@@ -952,6 +954,8 @@ class InflatePlan(_Packing):
         return buf.raw[:got.value]
 
     def run(self, d_src: int, d_dst: int = 0, stream: int = 0) -> None:
+        """stream (a hipStream_t as an int, e.g. torch.cuda.Stream().cuda_stream): the run is ordered in it like a
+        kernel, and on another stream than the plan's unfinished run or pack it waits for that on the device."""
         rc = lib.zsc_hip_inflate_plan_run(self._h, C.c_void_p(d_src), C.c_void_p(d_dst),
                                           C.c_void_p(stream))
         if rc != Z_OK:
@@ -1082,6 +1086,8 @@ class DeflatePlan(_Packing):
         lib.zsc_hip_deflate_plan_profile(self._h, 1 if enable else 0)
 
     def run(self, d_input: int, d_output: int, stream: int = 0) -> None:
+        """stream (a hipStream_t as an int, e.g. torch.cuda.Stream().cuda_stream): the run is ordered in it like a
+        kernel, and on another stream than the plan's unfinished run, verify or pack it waits for that on the device."""
         rc = lib.zsc_hip_deflate_plan_run(self._h, C.c_void_p(d_input), C.c_void_p(d_output),
                                           C.c_void_p(stream))
         if rc != Z_OK:
@@ -1147,7 +1153,8 @@ class DeflatePlan(_Packing):
     def verify(self, d_input: int, d_output: int, stream: int = 0) -> int:
         """After results(), any number of times: enqueue the verification of the streams at d_output (the
         run's output or a copy of it, with the plan's out_offsets) against the input at d_input.  Returns
-        the ZlibReturn: Z_STREAM_ERROR on a plan without verify_enable()."""
+        the ZlibReturn: Z_STREAM_ERROR on a plan without verify_enable().
+        stream: the verification is ordered in it like a kernel; the plan's next run, results() and close() wait for it."""
         return lib.zsc_hip_deflate_plan_verify(self._h, C.c_void_p(d_input), C.c_void_p(d_output), C.c_void_p(stream))
 
     def verify_results(self) -> List[dict]:

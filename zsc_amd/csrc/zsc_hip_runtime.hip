@@ -1597,6 +1597,73 @@ struct DevBuf {
 /* the longest buffer one plan entry may be: deflateBound of it stays below 2^29 bytes = 2^32 bits */
 #define ZSC_HIP_MAX_BUFFER 0x1ff00000u
 
+/* The streams rule (zsc_hip.h, "Streams"): a plan has one set of scratch, so what it enqueues is ordered on the
+ * device whatever streams it is given, and the host waits only in _results, the accessors and _destroy.  One of
+ * these per kind of work -- a plan's runs, its verifications, its packs: the stream the last enqueue of the kind
+ * went to and an event (hipEventDisableTiming) recorded behind it.  A plan that only ever sees one stream pays
+ * one event record per enqueue and never a hipStreamWaitEvent. */
+struct Enqueued {
+    hipEvent_t done = nullptr;
+    hipStream_t stream = nullptr;
+    bool pending = false;          /* enqueued since the host last waited for this kind */
+    std::vector<hipStream_t> left; /* streams a chain of runs has left behind since then (work_chain) */
+};
+
+/* the host waits for the work of the kind: before its results are read or its blocks go back to the cache */
+hipError_t work_wait(Enqueued &w)
+{
+    if (!w.pending)
+        return hipSuccess;
+    hipError_t rc = hipSuccess;
+    for (hipStream_t s : w.left) {
+        const hipError_t e = hipStreamSynchronize(s);
+        rc = rc == hipSuccess ? e : rc;
+    }
+    w.left.clear();
+    const hipError_t e = hipStreamSynchronize(w.stream);
+    w.pending = false;
+    return rc == hipSuccess ? e : rc;
+}
+
+/* what is enqueued on `st` from here on comes after the work of the kind, wherever that went: a wait on the
+ * device where it went to another stream (the same stream orders it by itself) */
+void work_order(Enqueued &w, hipStream_t st)
+{
+    if (!w.pending || w.stream == st)
+        return;
+    if (w.done == nullptr || hipStreamWaitEvent(st, w.done, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)work_wait(w); /* no event to wait for: the host waits */
+    }
+}
+
+/* the same before a run that follows the plan's earlier run: the runs form a chain, so the end of the last one
+ * is the end of them all; the stream the chain leaves is kept for work_wait, which waits for it too */
+void work_chain(Enqueued &w, hipStream_t st)
+{
+    work_order(w, st);
+    if (w.pending && w.stream != st && std::find(w.left.begin(), w.left.end(), w.stream) == w.left.end())
+        w.left.push_back(w.stream);
+}
+
+/* behind the last launch of an enqueue on `st` */
+void work_note(Enqueued &w, hipStream_t st)
+{
+    if (w.done == nullptr && hipEventCreateWithFlags(&w.done, hipEventDisableTiming) != hipSuccess)
+        w.done = nullptr; /* (the error stays for the caller's hipGetLastError; work_order then waits on the host) */
+    if (w.done)
+        (void)hipEventRecord(w.done, st);
+    w.stream = st;
+    w.pending = true;
+}
+
+void work_release(Enqueued &w)
+{
+    if (w.done)
+        (void)hipEventDestroy(w.done);
+    w = Enqueued();
+}
+
 /* a group of buffers that shares one set of scratch arrays */
 struct SubBatch {
     uint32_t first = 0, count = 0; /* buffers [first, first+count) of the plan */
@@ -1624,6 +1691,7 @@ struct PackState {
     uint64_t level_n[PK_MAX_LEVELS] = {0}, level_at[PK_MAX_LEVELS] = {0};
     hipEvent_t ev[2] = {nullptr, nullptr};
     hipStream_t stream = nullptr;
+    Enqueued work; /* the packs, for the plan's next run and its destroy */
     uint64_t scratch = 0;
 };
 
@@ -1650,6 +1718,7 @@ void pack_release(PackState &ps, uint64_t *scratch_bytes)
             (void)hipEventDestroy(e);
         e = nullptr;
     }
+    work_release(ps.work);
     if (scratch_bytes)
         *scratch_bytes -= ps.scratch;
     ps.scratch = 0;
@@ -1731,6 +1800,7 @@ ZlibReturn pack_enqueue(PackState &ps, const PkLens &lens, const void *d_sparse_
                            (uint8_t *)const_cast<void *>(d_sparse_image));
     }
     (void)hipEventRecord(ps.ev[1], st);
+    work_note(ps.work, st);
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
     return Z_OK;
 }
@@ -1829,6 +1899,7 @@ struct zsc_hip_deflate_plan {
     size_t events_used = 0;
     uint32_t profiled_runs = 0;
     hipStream_t last_stream = nullptr;
+    Enqueued ran; /* the runs; the verifications and packs keep their own (vf_work, pack.work) */
     uint64_t scratch_bytes = 0;
     /* the seek-point index (deflate_index.h), off unless zsc_hip_deflate_plan_index_enable was called */
     bool idx_on = false;
@@ -1862,6 +1933,7 @@ struct zsc_hip_deflate_plan {
     uint64_t vf_scratch = 0;      /* what of scratch_bytes verification holds */
     hipEvent_t vf_ev[2] = {nullptr, nullptr};
     hipStream_t vf_stream = nullptr;
+    Enqueued vf_work;
     /* packing (pack.h), off unless zsc_hip_deflate_plan_pack_enable was called */
     PackState pack;
 };
@@ -2001,6 +2073,13 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
                               const U32 *out_caps, I32 level, I32 window_bits, I32 mem_level,
                               ZlibStrategy strategy, const PlanRuns *runs);
 
+/* the host waits for everything the plan has enqueued, whatever streams it went to */
+static hipError_t plan_wait_all(zsc_hip_deflate_plan *pl)
+{
+    const hipError_t a = work_wait(pl->ran), b = work_wait(pl->vf_work), c = work_wait(pl->pack.work);
+    return a != hipSuccess ? a : b != hipSuccess ? b : c;
+}
+
 /* gives back what zsc_hip_deflate_plan_index_enable took (the caller has waited for the plan's work) */
 static void index_release(zsc_hip_deflate_plan *pl)
 {
@@ -2029,6 +2108,7 @@ static void verify_release(zsc_hip_deflate_plan *pl)
     pl->vf_on = false;
     pl->vf_valid = false;
     pl->vf_ran = false;
+    work_release(pl->vf_work);
     for (hipEvent_t &e : pl->vf_ev) {
         if (e)
             (void)hipEventDestroy(e);
@@ -2331,8 +2411,13 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
     ZSC_ASSERT(d_input != Z_NULL);
     ZSC_ASSERT(d_output != Z_NULL);
     hipStream_t st = (hipStream_t)hip_stream;
-    pl->last_stream = st;
     (void)hipGetLastError(); /* an error some earlier call on this thread left behind is not this run's */
+    /* one set of scratch: behind the plan's earlier run, and behind a verification or a pack that still reads the
+     * results and the block facts this run writes -- on the device, and only where they went to another stream */
+    work_chain(pl->ran, st);
+    work_order(pl->vf_work, st);
+    work_order(pl->pack.work, st);
+    pl->last_stream = st;
     const uint8_t *in = (const uint8_t *)d_input;
     uint8_t *out = (uint8_t *)d_output;
     ZdLevel cfg = kLevels[pl->level];
@@ -2488,6 +2573,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
                                (const DvfBuf *)pl->d_vf_bufs.p + sb.first, (DvfBlock *)pl->d_vf_facts.p,
                                (uint32_t *)pl->d_vf_nblk.p + sb.first, sb.nslots);
     }
+    work_note(pl->ran, st);
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
     return Z_OK;
 }
@@ -2497,7 +2583,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_results(zsc_hip_deflate_plan *pl, U32
 {
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
-    HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+    HIP_TRY(plan_wait_all(pl), return Z_STREAM_ERROR);
     std::vector<ZdResult> res(pl->count);
     if (pl->count)
         HIP_TRY(hipMemcpy(res.data(), pl->d_res.p, sizeof(ZdResult) * pl->count,
@@ -2588,9 +2674,8 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
     DeviceScope scope;
     if (!pl)
         return;
-    (void)hipStreamSynchronize(pl->last_stream); /* the blocks go back to the cache, not to hipFree */
-    if (pl->pack.ran)
-        (void)hipStreamSynchronize(pl->pack.stream);
+    /* the blocks go back to the cache, not to hipFree: the runs, the verifications and the packs are waited for */
+    (void)plan_wait_all(pl);
     for (SubBatch &sb : pl->subs) {
         sb.d_bufs.release();
         sb.d_tile_owner.release();
@@ -2617,6 +2702,7 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : pl->idx_events)
         (void)hipEventDestroy(e);
+    work_release(pl->ran);
     delete pl;
 }
 
@@ -2632,7 +2718,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_index_enable(zsc_hip_deflate_plan *pl
     chunk_bytes = dix_chunk_bytes(chunk_bytes);
     if (pl->idx_on && pl->idx_chunk == chunk_bytes)
         return Z_OK;
-    (void)hipStreamSynchronize(pl->last_stream);
+    (void)plan_wait_all(pl);
     index_release(pl);
     pl->idx_rec_off.assign((size_t)pl->count + 1u, 0);
     uint64_t max_slots = 1;
@@ -2787,7 +2873,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_verify_enable(zsc_hip_deflate_plan *p
         return Z_STREAM_ERROR;
     if (pl->vf_on)
         return Z_OK;
-    (void)hipStreamSynchronize(pl->last_stream);
+    (void)plan_wait_all(pl);
     uint64_t slots = 0;
     pl->vf_bufs.assign(pl->count, DvfBuf());
     for (uint32_t i = 0; i < pl->count; i++) {
@@ -2854,6 +2940,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_verify(zsc_hip_deflate_plan *pl, cons
                            (const ZdResult *)pl->d_res.p, (uint32_t)pl->wrap, (uint32_t)pl->wbits, (uint32_t)pl->level,
                            pl->strategy, (DvfResult *)pl->d_vf_res.p, pl->count);
     (void)hipEventRecord(pl->vf_ev[1], st);
+    work_note(pl->vf_work, st);
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
     return Z_OK;
 }
@@ -3877,6 +3964,7 @@ struct zsc_hip_inflate_plan {
     const void *last_src = nullptr;
     void *last_dst = nullptr;
     hipStream_t last_stream = nullptr;
+    Enqueued ran; /* the runs; the packs keep their own (pack.work) */
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     /* packing (pack.h), off unless zsc_hip_inflate_plan_pack_enable was called */
@@ -3902,6 +3990,13 @@ struct zsc_hip_inflate_plan {
                 d_cand.p, d_cused.p, d_creach.p, d_want.p, d_ring.p, d_win.p};
     }
 };
+
+/* the host waits for everything the plan has enqueued, whatever streams it went to */
+static hipError_t inflate_wait_all(zsc_hip_inflate_plan *pl)
+{
+    const hipError_t a = work_wait(pl->ran), b = work_wait(pl->pack.work);
+    return a != hipSuccess ? a : b;
+}
 
 static void inflate_plan_release(zsc_hip_inflate_plan *pl)
 {
@@ -4496,10 +4591,14 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     hipStream_t st = (hipStream_t)hip_stream;
-    pl->last_stream = st;
-    if (pl->count == 0)
+    if (pl->count == 0) {
+        pl->last_stream = st;
         return Z_OK;
+    }
     (void)hipGetLastError(); /* (see zsc_hip_deflate_plan_run) */
+    work_chain(pl->ran, st); /* (the same: one set of scratch, and a pack reads the results this run writes) */
+    work_order(pl->pack.work, st);
+    pl->last_stream = st;
     pl->last_src = d_src;
     pl->last_dst = d_dst;
     HIP_TRY(hipMemsetAsync(pl->d_resume.p, 0, sizeof(InfResume) * pl->count, st), return Z_STREAM_ERROR);
@@ -4534,6 +4633,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         inflate_launch(pl, d_src, d_dst, st, true);
     (void)hipEventRecord(pl->ev1, st);
     pl->timed = true;
+    work_note(pl->ran, st);
     HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
     return Z_OK;
 }
@@ -4543,7 +4643,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_results(zsc_hip_inflate_plan *pl, U32
 {
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
-    HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+    HIP_TRY(inflate_wait_all(pl), return Z_STREAM_ERROR);
     /* streams that hit a data error and found a flush marker behind it (inflateSync) are
      * inflated again from there, as zsc_uncompress's loop does (src/zsc_uncompr.c:104-125);
      * every round consumes at least the marker, so this ends */
@@ -4584,11 +4684,10 @@ extern "C" void zsc_hip_inflate_plan_destroy(zsc_hip_inflate_plan *pl)
     DeviceScope scope;
     if (!pl)
         return;
-    (void)hipStreamSynchronize(pl->last_stream);
-    if (pl->pack.ran)
-        (void)hipStreamSynchronize(pl->pack.stream);
+    (void)inflate_wait_all(pl); /* the blocks go back to the cache: the runs and the packs are waited for */
     inflate_plan_release(pl);
     pack_release(pl->pack, &pl->scratch_bytes);
+    work_release(pl->ran);
     if (pl->ev0)
         (void)hipEventDestroy(pl->ev0);
     if (pl->ev1)
@@ -4607,7 +4706,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_sections(zsc_hip_inflate_plan *pl, U3
             sections[i] = 0;
         return Z_OK;
     }
-    HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+    HIP_TRY(inflate_wait_all(pl), return Z_STREAM_ERROR);
     HIP_TRY(hipMemcpy(sections, pl->d_nsec.p, 4ull * pl->count, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
     return Z_OK;
 }
@@ -4620,7 +4719,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_members(zsc_hip_inflate_plan *pl, U32
         return Z_STREAM_ERROR;
     std::vector<MemFile> mf(pl->count, MemFile{0, 0, 0, 0});
     if ((pl->last_dst || pl->size_ran) && pl->count) {
-        HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+        HIP_TRY(inflate_wait_all(pl), return Z_STREAM_ERROR);
         HIP_TRY(hipMemcpy(mf.data(), pl->d_mfiles.p, sizeof(MemFile) * pl->count, hipMemcpyDeviceToHost),
                 return Z_STREAM_ERROR);
     }
@@ -4643,7 +4742,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_data_errors(zsc_hip_inflate_plan *pl,
             errors[i] = 0;
         return Z_OK;
     }
-    HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+    HIP_TRY(inflate_wait_all(pl), return Z_STREAM_ERROR);
     std::vector<InfResume> rs(pl->count);
     HIP_TRY(hipMemcpy(rs.data(), pl->d_resume.p, sizeof(InfResume) * pl->count, hipMemcpyDeviceToHost),
             return Z_STREAM_ERROR);
@@ -4669,7 +4768,7 @@ static ZlibReturn idx_records(zsc_hip_inflate_plan *pl, U32 stream, const std::v
         return Z_STREAM_ERROR;
     auto hit = pl->idx_recs.find(stream);
     if (hit == pl->idx_recs.end()) {
-        HIP_TRY(hipStreamSynchronize(pl->last_stream), return Z_STREAM_ERROR);
+        HIP_TRY(inflate_wait_all(pl), return Z_STREAM_ERROR);
         uint32_t n = 0;
         HIP_TRY(hipMemcpy(&n, (const uint32_t *)pl->d_nsec.p + stream, 4, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
         std::vector<ZidxRec> r(n);
@@ -4862,7 +4961,7 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_dict_enable(zsc_hip_inflate_plan *pl,
         return Z_MEM_ERROR;
     }
     /* the set the plan had, if any, is replaced (its last run may still be reading it) */
-    (void)hipStreamSynchronize(pl->last_stream);
+    (void)inflate_wait_all(pl);
     std::swap(static_cast<DevBuf &>(pl->d_dict_img), img);
     std::swap(static_cast<DevBuf &>(pl->d_dict_tab), d_tab);
     std::swap(static_cast<DevBuf &>(pl->d_dict_of), d_of);
