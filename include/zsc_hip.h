@@ -123,7 +123,7 @@ ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources, U32 *so
  *     for the plan's last run: a run that another _run follows before _results is left where its first pass
  *     got to.
  *   - a plan has ONE set of scratch.  A _run enqueued on another stream than the plan's unfinished earlier
- *     work -- a run, a verification or a pack -- waits for that work on the device (an event behind each
+ *     work -- a run, a verification, a pack or a _bgzf -- waits for that work on the device (an event behind each
  *     enqueue, hipStreamWaitEvent only where the streams differ); the host does not wait.  A plan that only
  *     ever sees one stream enqueues nothing for this but one event record per call.
  *   - _results, every accessor and _destroy wait, on the host, for all of the plan's work, whatever streams
@@ -770,6 +770,64 @@ ZlibReturn zsc_hip_uncompress_batch_packed(U32 count, const U8 *sources, const u
                                            const U32 *source_lens, const U32 *dest_caps, U8 *dest,
                                            uint64_t dest_cap, uint64_t *dest_offsets, U32 *dest_lens,
                                            U32 *consumed, I32 *statuses, I32 window_bits, U32 align);
+
+/* BGZF files --------------------------------------------------------------------
+ *
+ * A gzip deflate plan's streams written out as BGZF files -- the block-gzip container of bgzip, BAM and tabix --
+ * on the device (zsc_amd/csrc/bgzf.h).  A file is a run of consecutive buffers of the
+ * plan, file_first[f] .. file_first[f + 1] (a run may be empty); its image is one member per buffer, in buffer
+ * order, and the 28 bytes that end a BGZF file:
+ *
+ *   member header (18): 1f 8b 08 04 | 00 00 00 00 | XFL | ff | 06 00 | 42 43 02 00 | BSIZE lo, hi
+ *      XFL   = byte 8 of the plan's own stream for that buffer
+ *      BSIZE = the member's length - 1; the member of a stream of out_len bytes is L = out_len + 8 bytes long
+ *   member body:        the plan's stream from byte 10 to its end (deflate data, CRC-32, ISIZE), unchanged
+ *   end of file (28):   1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00
+ *
+ * which is byte for byte what the reference writes when it is given that FEXTRA field in a gz_header.  Files
+ * start at multiples of align (a power of two from 1 to 4096, as with _pack) and the bytes from a file's end to
+ * the next file's start are zeros.  A file FAILS with Z_BUF_ERROR where one of its buffers has a status other
+ * than Z_OK or an L above 65 536 (BSIZE has 16 bits; the caller picks shorter buffers): it takes no room in the
+ * image, like a failed item of _pack, and the other files are what they are without it.  A members plan
+ * (zsc_hip_inflate_plan_create_members) reads such a file by its BSIZE fields, each member decoded once.
+ *
+ * _bgzf_enable: before _run.  Z_STREAM_ERROR, with the plan left as it was, for a plan whose wrapper is not
+ *   gzip, a plan of sections, a source_lens[i] above 65 536, a file_first that does not ascend from 0 to count,
+ *   or a bad align.  Calling it again replaces the partition.  Allocates 20 bytes per buffer and 24 per file,
+ *   and 8 per 1 024 files for the scan's partial sums, counted in _scratch_bytes.  Independent of _pack_enable,
+ *   _index_enable and _verify_enable: all may be on.  A plan that never calls it allocates and launches exactly
+ *   what it did without these functions.
+ * _bgzf: asynchronous on hip_stream; enqueues kernels only -- no allocation, no synchronisation, no copy from
+ *   or to the host.  Valid after a _run on the same stream or after _results, any number of times.  d_output is
+ *   the run's output or a copy of it at the plan's offsets; of each stream the whole 16-byte granules that hold
+ *   one of its bytes are read.  d_image is 16-byte aligned and image_cap bytes long: bytes [0, total) are each
+ *   written exactly once and nothing at or behind total; with total > image_cap nothing is written at all.
+ *   Ordered against the plan's runs like a pack (see "Streams").
+ * _bgzf_results: waits for the last _bgzf.  Every pointer may be NULL.  file_offsets[f]: where file f starts,
+ *   file_offsets[nfiles] == *total; file_lens[f]: its length without the zeros behind it, 0 for a failed file;
+ *   file_statuses[f]: Z_OK or Z_BUF_ERROR; member_offsets[i]: where buffer i's member starts -- for a member of
+ *   a failed file the file's offset --, which with source_lens gives a caller BGZF virtual offsets; ms: the
+ *   device time of that _bgzf's launches.  Z_BUF_ERROR where total > image_cap, the tables filled all the
+ *   same; Z_STREAM_ERROR on a plan that never enabled this or never called _bgzf. */
+ZlibReturn zsc_hip_deflate_plan_bgzf_enable(zsc_hip_deflate_plan *plan, U32 nfiles, const U32 *file_first,
+                                            U32 align);
+ZlibReturn zsc_hip_deflate_plan_bgzf(zsc_hip_deflate_plan *plan, const void *d_output, void *d_image,
+                                     uint64_t image_cap, void *hip_stream);
+ZlibReturn zsc_hip_deflate_plan_bgzf_results(zsc_hip_deflate_plan *plan, uint64_t *file_offsets,
+                                             uint64_t *file_lens, I32 *file_statuses, uint64_t *member_offsets,
+                                             uint64_t *total, float *ms);
+
+/* Host memory: nfiles files compressed into nfiles BGZF files.  File f (sources[f], source_lens[f] bytes) is
+ * uploaded once, at a 16-byte aligned offset, and cut where it lies into buffers of block_bytes -- a multiple
+ * of 16 from 16 to 65 536; 0 means 65 280, bgzip's value -- then one plan, one run, one _bgzf and one copy back
+ * per file.  dest_lens[f]: in, the room at dests[f]; out, the file's length.  statuses[f] (may be NULL): Z_OK;
+ * Z_BUF_ERROR where the file failed (a block that does not fit a member: pick a smaller block_bytes; the
+ * length is then 0) or where the room is too small (nothing is copied, the length says what it takes).  An
+ * empty file is the 28 end-of-file bytes.  Returns Z_OK when the batch ran.  Level 0 is Z_STREAM_ERROR, as in
+ * the packed batch. */
+ZlibReturn zsc_hip_bgzf_compress_batch(U32 nfiles, const U8 *const *sources, const uint64_t *source_lens,
+                                       U8 *const *dests, uint64_t *dest_lens, I32 *statuses, I32 level,
+                                       I32 mem_level, ZlibStrategy strategy, U32 block_bytes);
 
 /* preset dictionaries (decompression only) ---------------------------------
  *

@@ -30,6 +30,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
 * :func:`compress_batch_packed`, :func:`uncompress_batch_packed`, :func:`unpack` -- batches as ONE image with a
   table of offsets: one copy to the device and one back whatever the count (``DeflatePlan.pack_enable`` /
   ``pack`` / ``pack_results``, the same on :class:`InflatePlan`);
+* :func:`bgzf_compress_batch` -- files written as BGZF, the block-gzip container of bgzip, BAM and tabix, which a
+  members plan reads back member by member (``DeflatePlan.bgzf_enable`` / ``bgzf`` / ``bgzf_results``);
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -50,5 +52,6 @@ from .api import (  # noqa: F401
     compress_batch_verified, VERIFY_OK, VERIFY_SKIPPED, VERIFY_HEADER, VERIFY_BLOCK_HDR, VERIFY_CODES, VERIFY_LITERAL,
     VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH, VERIFY_BIT_END, VERIFY_TRAILER,
     PACK_TILE, unpack, compress_batch_packed, uncompress_batch_packed, PackedCallError,
+    bgzf_compress_batch,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

@@ -172,6 +172,11 @@ def _load() -> C.CDLL:
         getattr(L, f"zsc_hip_{kind}_plan_pack_enable").argtypes = [C.c_void_p, C.c_uint32]
         getattr(L, f"zsc_hip_{kind}_plan_pack").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         getattr(L, f"zsc_hip_{kind}_plan_pack_results").argtypes = [C.c_void_p, u64p, u64p, C.POINTER(C.c_float)]
+    L.zsc_hip_deflate_plan_bgzf_enable.argtypes = [C.c_void_p, C.c_uint32, u32p, C.c_uint32]
+    L.zsc_hip_deflate_plan_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zsc_hip_deflate_plan_bgzf_results.argtypes = [C.c_void_p, u64p, u64p, i32p, u64p, u64p, C.POINTER(C.c_float)]
+    L.zsc_hip_bgzf_compress_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u64p, C.POINTER(C.c_void_p), u64p,
+                                              i32p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
     L.zsc_hip_unpack.argtypes = [C.c_uint32, C.c_void_p, u64p, u32p, C.c_void_p, u64p, C.c_void_p]
     L.zsc_hip_compress_batch_packed.argtypes = [C.c_uint32, C.c_char_p, u64p, C.c_void_p, C.c_uint64, u64p, i32p,
                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
@@ -723,6 +728,29 @@ def compress_batch_packed(sources, level: int = 6, window_bits: int = DEF_WBITS,
     return dst.raw[:off[n]], list(off), list(stat)[:n]
 
 
+def bgzf_compress_batch(files: Sequence[bytes], level: int = 6, block_bytes: int = 65280,
+                        mem_level: int = DEF_MEM_LEVEL, strategy: int = Z_DEFAULT_STRATEGY,
+                        dest_caps: Sequence[int] | None = None) -> Tuple[List[bytes], List[int]]:
+    """zsc_hip_bgzf_compress_batch: every file compressed into a BGZF file of its own, cut into members of
+    block_bytes of input (a multiple of 16 up to 65 536; 65 280 is bgzip's).  Returns (files, statuses): a file
+    whose status is Z_BUF_ERROR is b"" -- one of its blocks did not fit a member (pick a smaller block_bytes),
+    or dest_caps[f] (default: the worst case) was too small.  PackedCallError where the call as a whole fails."""
+    n = len(files)
+    bb = block_bytes or 65280
+    if dest_caps is None:
+        dest_caps = [((len(f) + bb - 1) // bb) * 65536 + 28 for f in files]
+    bufs = [C.create_string_buffer(max(c, 1)) for c in dest_caps]
+    srcs = (C.c_char_p * max(n, 1))(*files)
+    slen = (C.c_uint64 * max(n, 1))(*[len(f) for f in files])
+    dsts = (C.c_void_p * max(n, 1))(*[C.addressof(b) for b in bufs])
+    dlen = (C.c_uint64 * max(n, 1))(*dest_caps)
+    stat = (C.c_int32 * max(n, 1))()
+    rc = lib.zsc_hip_bgzf_compress_batch(n, srcs, slen, dsts, dlen, stat, level, mem_level, strategy, block_bytes)
+    if rc != Z_OK:
+        raise PackedCallError("zsc_hip_bgzf_compress_batch", rc, [])
+    return [b.raw[:dlen[f]] if stat[f] == Z_OK else b"" for f, b in enumerate(bufs)], list(stat)[:n]
+
+
 def uncompress_batch_packed(image: bytes, offsets: Sequence[int], lens: Sequence[int], dest_caps: Sequence[int],
                             window_bits: int = DEF_WBITS, align: int = 1, dest_cap: Optional[int] = None):
     """zsc_hip_uncompress_batch_packed: uncompress_batch with one copy to the device and one back.  Stream i is
@@ -1190,6 +1218,53 @@ class DeflatePlan(_Packing):
         if rc != Z_OK:
             raise RuntimeError(f"zsc_hip_deflate_plan_verify_blocks failed: {rc}")
         return [(b.bit_off, b.in_begin, b.in_len, b.type_last & 0xff, b.type_last >> 8) for b in blocks[:n.value]]
+
+    def bgzf_enable(self, file_first: Sequence[int], align: int = 1) -> None:
+        """Before run(), on a gzip plan (window_bits 31) whose buffers are 65 536 bytes at the most: the plan can
+        write its streams as BGZF files, file f the buffers file_first[f] .. file_first[f + 1] (nfiles + 1
+        values ascending from 0 to count), each file at a multiple of align.  Calling it again replaces the
+        partition.  ValueError, the plan as it was, where the library refuses."""
+        nfiles = len(file_first) - 1
+        if nfiles < 0:
+            raise ValueError("file_first holds nfiles + 1 values")
+        rc = lib.zsc_hip_deflate_plan_bgzf_enable(self._h, nfiles, (C.c_uint32 * (nfiles + 1))(*file_first), align)
+        if rc != Z_OK:
+            raise ValueError(f"zsc_hip_deflate_plan_bgzf_enable failed: {rc}")
+        self._bgzf_files = nfiles
+
+    def bgzf(self, d_output: int, d_image: int, cap: int, stream: int = 0) -> int:
+        """After run() on the same stream, or after results(), any number of times: enqueue the writing of the
+        files from the streams at d_output (the run's output or a copy of it, with the plan's out_offsets) into
+        the cap bytes at d_image (16-byte aligned).  Returns the ZlibReturn: Z_STREAM_ERROR on a plan without
+        bgzf_enable().  stream: ordered in it like a kernel; the plan's next run, results() and close() wait."""
+        return lib.zsc_hip_deflate_plan_bgzf(self._h, C.c_void_p(d_output), C.c_void_p(d_image), cap, C.c_void_p(stream))
+
+    def bgzf_results(self) -> dict:
+        """Waits for the last bgzf(): {"file_offsets" (nfiles + 1), "file_lens", "file_statuses", "member_offsets"
+        (count), "total"}.  A failed file (Z_BUF_ERROR: a buffer that is not Z_OK or whose member would pass
+        65 536 bytes) has length 0.  BufferError, with .tables, where the image was longer than cap (nothing was
+        written)."""
+        nf = getattr(self, "_bgzf_files", 0)
+        foff, flen = (C.c_uint64 * (nf + 1))(), (C.c_uint64 * max(nf, 1))()
+        fst, moff = (C.c_int32 * max(nf, 1))(), (C.c_uint64 * max(self.count, 1))()
+        total, ms = C.c_uint64(), C.c_float()
+        rc = lib.zsc_hip_deflate_plan_bgzf_results(self._h, foff, flen, fst, moff, C.byref(total), C.byref(ms))
+        self._bgzf_ms = ms.value
+        tables = {"file_offsets": list(foff), "file_lens": list(flen)[:nf], "file_statuses": list(fst)[:nf],
+                  "member_offsets": list(moff)[:self.count], "total": total.value}
+        if rc == Z_BUF_ERROR:
+            err = BufferError(f"the BGZF image takes {total.value} bytes")
+            err.tables = tables
+            raise err
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_deflate_plan_bgzf_results failed: {rc}")
+        return tables
+
+    def bgzf_ms(self) -> float:
+        """After bgzf_results(): device time of that bgzf()'s launches, in milliseconds."""
+        if getattr(self, "_bgzf_ms", None) is None:
+            raise RuntimeError("no bgzf_results() yet")
+        return self._bgzf_ms
 
     def close(self) -> None:
         if self._h:

@@ -37,6 +37,7 @@
 #include "deflate_index.h"
 #include "deflate_verify.h"
 #include "pack.h"
+#include "bgzf.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "lz_parse_pipe.h"
@@ -826,6 +827,24 @@ __global__ __launch_bounds__(64) void k_pack_apply(PkLens lens, uint32_t align, 
 __global__ __launch_bounds__(64) void k_pack_move(PkMove M, uint8_t *dense, uint8_t *sparse)
 {
     pk_move_tile(M, dense, sparse, blockIdx.x);
+}
+
+/* kernels 4m-4o (bgzf.h): a gzip plan's streams as BGZF files, only for a plan with zsc_hip_deflate_plan_bgzf_enable.
+ * 4m one wavefront per file: its length; the files' offsets are 4i-4k over those lengths; 4n one wavefront per
+ * file (and one more): the offsets of the members and the tails; 4o one wavefront per tile of the image */
+__global__ __launch_bounds__(64) void k_bgzf_file_len(BzFiles F, uint64_t *file_len)
+{
+    bz_file_len(F, blockIdx.x, file_len);
+}
+
+__global__ __launch_bounds__(64) void k_bgzf_member_off(BzFiles F, const uint64_t *file_off, uint64_t *parts)
+{
+    bz_member_off(F, blockIdx.x, file_off, parts);
+}
+
+__global__ __launch_bounds__(64) void k_bgzf_move(BzMove M, uint8_t *image, const uint8_t *out)
+{
+    bz_move_tile(M, image, out, blockIdx.x);
 }
 
 /* one stream of an inflate batch */
@@ -1752,21 +1771,30 @@ ZlibReturn pack_setup(PackState &ps, uint32_t count, U32 align, const uint64_t *
     return Z_OK;
 }
 
-/* the dense offsets of the items whose lengths `lens` names: reduce up the levels, scan the top one, apply down */
+/* An exclusive prefix sum of level_n[0] values into out0 (one more entry: the sum): reduce up the levels, scan the
+ * top one, apply down.  The values are vals0[] or, without vals0, the lengths `lens` names rounded up to align;
+ * out0 may be vals0.  sums: the levels above, level k at level_at[k]. */
+void scan_enqueue(uint32_t levels, const uint64_t *level_n, const uint64_t *level_at, uint64_t *sums,
+                  const PkLens &lens, uint32_t align, uint64_t *vals0, uint64_t *out0, hipStream_t st)
+{
+    auto vals = [&](uint32_t k) { return k == 0 ? vals0 : sums + level_at[k]; };
+    auto out = [&](uint32_t k) { return k == 0 ? out0 : sums + level_at[k]; };
+    for (uint32_t k = 0; k + 1u < levels; k++)
+        hipLaunchKernelGGL(k_pack_reduce, dim3((uint32_t)level_n[k + 1u]), dim3(64), 0, st, lens, align,
+                           (const uint64_t *)vals(k), level_n[k], vals(k + 1u));
+    const uint32_t top = levels - 1u;
+    hipLaunchKernelGGL(k_pack_scan_sums, dim3(1), dim3(64), 0, st, lens, align, (const uint64_t *)vals(top),
+                       level_n[top], out(top));
+    for (uint32_t k = top; k-- > 0;)
+        hipLaunchKernelGGL(k_pack_apply, dim3((uint32_t)level_n[k + 1u]), dim3(64), 0, st, lens, align,
+                           (const uint64_t *)vals(k), level_n[k], (const uint64_t *)vals(k + 1u), out(k));
+}
+
+/* the dense offsets of the items whose lengths `lens` names */
 void pack_scan_enqueue(const PackState &ps, const PkLens &lens, hipStream_t st)
 {
-    uint64_t *const sums = (uint64_t *)ps.d_sums.p;
-    auto vals = [&](uint32_t k) { return k == 0 ? (uint64_t *)nullptr : sums + ps.level_at[k]; };
-    for (uint32_t k = 0; k + 1u < ps.levels; k++)
-        hipLaunchKernelGGL(k_pack_reduce, dim3((uint32_t)ps.level_n[k + 1u]), dim3(64), 0, st, lens, ps.align,
-                           (const uint64_t *)vals(k), ps.level_n[k], vals(k + 1u));
-    const uint32_t top = ps.levels - 1u;
-    hipLaunchKernelGGL(k_pack_scan_sums, dim3(1), dim3(64), 0, st, lens, ps.align, (const uint64_t *)vals(top),
-                       ps.level_n[top], top == 0 ? (uint64_t *)ps.d_off.p : vals(top));
-    for (uint32_t k = top; k-- > 0;)
-        hipLaunchKernelGGL(k_pack_apply, dim3((uint32_t)ps.level_n[k + 1u]), dim3(64), 0, st, lens, ps.align,
-                           (const uint64_t *)vals(k), ps.level_n[k], (const uint64_t *)vals(k + 1u),
-                           k == 0 ? (uint64_t *)ps.d_off.p : vals(k));
+    scan_enqueue(ps.levels, ps.level_n, ps.level_at, (uint64_t *)ps.d_sums.p, lens, ps.align, nullptr,
+                 (uint64_t *)ps.d_off.p, st);
 }
 
 ZlibReturn pack_enqueue(PackState &ps, const PkLens &lens, const void *d_sparse_image, void *d_packed,
@@ -1866,6 +1894,44 @@ bool unpack_table(uint32_t count, const uint64_t *packed_offsets, const U32 *len
     return true;
 }
 
+/* BGZF files (bgzf.h): what a gzip deflate plan holds for them */
+struct BgzfState {
+    bool on = false, ran = false;
+    uint32_t count = 0, nfiles = 0, align = 0;
+    std::vector<uint32_t> file_first; /* nfiles + 1 */
+    uint64_t max_total = 0;           /* the most the image takes */
+    uint64_t cap = 0;                 /* image_cap of the last _bgzf */
+    DevBuf d_first;                   /* file_first */
+    DevBuf d_file_off;                /* nfiles + 1: the files' lengths, scanned in place into their offsets */
+    DevBuf d_parts;                   /* count + nfiles + 1 offsets of the members and the tails */
+    DevBuf d_what;                    /* count + nfiles: what each part is */
+    DevBuf d_slots;                   /* count slot offsets */
+    DevBuf d_sums;                    /* the scan's levels above the files */
+    uint32_t levels = 1;
+    uint64_t level_n[PK_MAX_LEVELS] = {0}, level_at[PK_MAX_LEVELS] = {0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    Enqueued work; /* the _bgzf calls, for the plan's next run and its destroy */
+    uint64_t scratch = 0;
+};
+
+/* (the caller has waited for the work) */
+void bgzf_release(BgzfState &bs, uint64_t *scratch_bytes)
+{
+    for (DevBuf *b : {&bs.d_first, &bs.d_file_off, &bs.d_parts, &bs.d_what, &bs.d_slots, &bs.d_sums})
+        b->release();
+    for (hipEvent_t &e : bs.ev) {
+        if (e)
+            (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    work_release(bs.work);
+    if (scratch_bytes)
+        *scratch_bytes -= bs.scratch;
+    bs.scratch = 0;
+    bs.on = bs.ran = false;
+}
+
 } // namespace
 
 struct zsc_hip_deflate_plan {
@@ -1936,6 +2002,8 @@ struct zsc_hip_deflate_plan {
     Enqueued vf_work;
     /* packing (pack.h), off unless zsc_hip_deflate_plan_pack_enable was called */
     PackState pack;
+    /* BGZF files (bgzf.h), off unless zsc_hip_deflate_plan_bgzf_enable was called */
+    BgzfState bgzf;
 };
 
 /* The LDS geometry the pipeline runs in when nothing is said (ZSC_HIP_SEG_RING).  The narrow ring pays through
@@ -2076,8 +2144,9 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
 /* the host waits for everything the plan has enqueued, whatever streams it went to */
 static hipError_t plan_wait_all(zsc_hip_deflate_plan *pl)
 {
-    const hipError_t a = work_wait(pl->ran), b = work_wait(pl->vf_work), c = work_wait(pl->pack.work);
-    return a != hipSuccess ? a : b != hipSuccess ? b : c;
+    const hipError_t a = work_wait(pl->ran), b = work_wait(pl->vf_work), c = work_wait(pl->pack.work),
+                     d = work_wait(pl->bgzf.work);
+    return a != hipSuccess ? a : b != hipSuccess ? b : c != hipSuccess ? c : d;
 }
 
 /* gives back what zsc_hip_deflate_plan_index_enable took (the caller has waited for the plan's work) */
@@ -2417,6 +2486,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
     work_chain(pl->ran, st);
     work_order(pl->vf_work, st);
     work_order(pl->pack.work, st);
+    work_order(pl->bgzf.work, st);
     pl->last_stream = st;
     const uint8_t *in = (const uint8_t *)d_input;
     uint8_t *out = (uint8_t *)d_output;
@@ -2698,6 +2768,7 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
     index_release(pl);
     verify_release(pl);
     pack_release(pl->pack, &pl->scratch_bytes);
+    bgzf_release(pl->bgzf, &pl->scratch_bytes);
     for (hipEvent_t e : pl->events)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : pl->idx_events)
@@ -3030,6 +3101,168 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_pack_results(zsc_hip_deflate_plan *pl
     DeviceScope scope;
     ZSC_ASSERT(pl != Z_NULL);
     return pack_fetch(pl->pack, offsets, total, ms);
+}
+
+/* ---- BGZF files from a gzip deflate plan (bgzf.h) --------------------------------------------- */
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_bgzf_enable(zsc_hip_deflate_plan *pl, U32 nfiles, const U32 *file_first,
+                                                       U32 align)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(file_first != Z_NULL);
+    if (pl->wrap != 2 || pl->sectioned || !pack_align_ok(align) || file_first[0] != 0u ||
+        file_first[nfiles] != pl->count)
+        return Z_STREAM_ERROR;
+    for (U32 f = 0; f < nfiles; f++)
+        if (file_first[f + 1u] < file_first[f])
+            return Z_STREAM_ERROR;
+    for (uint32_t i = 0; i < pl->count; i++)
+        if (pl->bufs[i].in_len > BZ_MAX_MEMBER)
+            return Z_STREAM_ERROR;
+    /* the new partition beside the old one, which stays where anything fails */
+    BgzfState nb;
+    nb.count = pl->count;
+    nb.nfiles = nfiles;
+    nb.align = align;
+    nb.file_first.assign(file_first, file_first + nfiles + 1u);
+    const uint64_t nparts = (uint64_t)pl->count + nfiles;
+    if (nparts > 0x7fffffffull)
+        return Z_MEM_ERROR;
+    std::vector<uint32_t> what((size_t)std::max<uint64_t>(nparts, 1));
+    std::vector<uint64_t> slots(std::max<uint32_t>(pl->count, 1));
+    for (U32 f = 0; f < nfiles; f++) {
+        uint64_t most = BZ_TAIL;
+        for (uint32_t i = file_first[f]; i < file_first[f + 1u]; i++) {
+            what[(size_t)i + f] = i;
+            most += std::min<uint64_t>((uint64_t)pl->bufs[i].out_cap + (BZ_HEAD - BZ_SKIP), BZ_MAX_MEMBER);
+        }
+        what[(size_t)file_first[f + 1u] + f] = BZ_PART_TAIL;
+        nb.max_total += (most + (align - 1u)) & ~(uint64_t)(align - 1u);
+    }
+    for (uint32_t i = 0; i < pl->count; i++)
+        slots[i] = pl->bufs[i].out_off;
+    nb.levels = pk_scan_levels(nfiles, nb.level_n);
+    uint64_t nsums = 0;
+    for (uint32_t k = 1; k < nb.levels; k++) {
+        nb.level_at[k] = nsums;
+        nsums += nb.level_n[k] + 1u;
+    }
+    bool ok = nb.d_first.ensure(((uint64_t)nfiles + 1u) * 4u) && nb.d_file_off.ensure(((uint64_t)nfiles + 1u) * 8u) &&
+              nb.d_parts.ensure((nparts + 1u) * 8u) && nb.d_what.ensure(what.size() * 4u) &&
+              nb.d_slots.ensure(slots.size() * 8u) && nb.d_sums.ensure(std::max<uint64_t>(nsums, 1) * 8u);
+    ok = ok && hipMemcpy(nb.d_first.p, file_first, ((size_t)nfiles + 1u) * 4u, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(nb.d_what.p, what.data(), what.size() * 4u, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(nb.d_slots.p, slots.data(), slots.size() * 8u, hipMemcpyHostToDevice) == hipSuccess &&
+         hipEventCreate(&nb.ev[0]) == hipSuccess && hipEventCreate(&nb.ev[1]) == hipSuccess;
+    nb.scratch = nb.d_first.bytes + nb.d_file_off.bytes + nb.d_parts.bytes + nb.d_what.bytes + nb.d_slots.bytes +
+                 nb.d_sums.bytes;
+    if (!ok) {
+        (void)hipGetLastError();
+        bgzf_release(nb, nullptr);
+        return Z_MEM_ERROR;
+    }
+    if (pl->bgzf.on) { /* the partition of before goes, once what was enqueued with it has run */
+        (void)work_wait(pl->bgzf.work);
+        bgzf_release(pl->bgzf, &pl->scratch_bytes);
+    }
+    pl->bgzf = nb;
+    pl->bgzf.on = true;
+    pl->scratch_bytes += nb.scratch;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_bgzf(zsc_hip_deflate_plan *pl, const void *d_output, void *d_image,
+                                                uint64_t image_cap, void *hip_stream)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    BgzfState &bs = pl->bgzf;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!bs.on || ((uintptr_t)d_image & 15u) || ((uintptr_t)d_output & 15u))
+        return Z_STREAM_ERROR;
+    /* the grid comes from the capacity; what the image can be at the most bounds it */
+    const uint64_t tiles = (std::min(image_cap, bs.max_total) + PK_TILE - 1u) / PK_TILE;
+    if (tiles > 0x7fffffffull)
+        return Z_MEM_ERROR;
+    if (tiles && (d_image == Z_NULL || d_output == Z_NULL))
+        return Z_STREAM_ERROR;
+    (void)hipGetLastError();
+    if (bs.ran && bs.stream != st) /* the tables of the one before may still be in use */
+        HIP_TRY(hipStreamSynchronize(bs.stream), return Z_STREAM_ERROR);
+    bs.stream = st;
+    bs.ran = true;
+    bs.cap = image_cap;
+    (void)hipEventRecord(bs.ev[0], st);
+    BzFiles F;
+    F.rec = (const uint32_t *)pl->d_res.p;
+    F.file_first = (const uint32_t *)bs.d_first.p;
+    F.nfiles = bs.nfiles;
+    F.count = bs.count;
+    F.align = bs.align;
+    uint64_t *const file_off = (uint64_t *)bs.d_file_off.p;
+    if (bs.nfiles)
+        hipLaunchKernelGGL(k_bgzf_file_len, dim3(bs.nfiles), dim3(64), 0, st, F, file_off);
+    const PkLens none = {nullptr, 0u, 0u, PK_NO_STATUS};
+    scan_enqueue(bs.levels, bs.level_n, bs.level_at, (uint64_t *)bs.d_sums.p, none, 1u, file_off, file_off, st);
+    hipLaunchKernelGGL(k_bgzf_member_off, dim3(bs.nfiles + 1u), dim3(64), 0, st, F, (const uint64_t *)file_off,
+                       (uint64_t *)bs.d_parts.p);
+    if (tiles) {
+        BzMove M;
+        M.parts = (const uint64_t *)bs.d_parts.p;
+        M.what = (const uint32_t *)bs.d_what.p;
+        M.slot = (const uint64_t *)bs.d_slots.p;
+        M.nparts = bs.count + bs.nfiles;
+        M.cap = image_cap;
+        hipLaunchKernelGGL(k_bgzf_move, dim3((uint32_t)tiles), dim3(64), 0, st, M, (uint8_t *)d_image,
+                           (const uint8_t *)d_output);
+    }
+    (void)hipEventRecord(bs.ev[1], st);
+    work_note(bs.work, st);
+    HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_bgzf_results(zsc_hip_deflate_plan *pl, uint64_t *file_offsets,
+                                                        uint64_t *file_lens, I32 *file_statuses,
+                                                        uint64_t *member_offsets, uint64_t *total, float *ms)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    BgzfState &bs = pl->bgzf;
+    if (ms)
+        *ms = 0.f;
+    if (total)
+        *total = 0;
+    if (!bs.on || !bs.ran)
+        return Z_STREAM_ERROR;
+    HIP_TRY(hipStreamSynchronize(bs.stream), return Z_STREAM_ERROR);
+    const size_t nparts = (size_t)bs.count + bs.nfiles;
+    std::vector<uint64_t> parts(nparts + 1u);
+    HIP_TRY(hipMemcpy(parts.data(), bs.d_parts.p, parts.size() * 8u, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    const uint64_t tot = parts[nparts];
+    for (uint32_t f = 0; f < bs.nfiles; f++) {
+        const uint32_t first = bs.file_first[f], end = bs.file_first[f + 1u];
+        /* a sound file has its tail; a failed one has nothing */
+        const uint64_t at = parts[(size_t)first + f], tail = parts[(size_t)end + f];
+        const bool sound = parts[(size_t)end + f + 1u] > tail;
+        if (file_offsets)
+            file_offsets[f] = at;
+        if (file_lens)
+            file_lens[f] = sound ? tail + BZ_TAIL - at : 0u;
+        if (file_statuses)
+            file_statuses[f] = sound ? Z_OK : Z_BUF_ERROR;
+        if (member_offsets)
+            for (uint32_t i = first; i < end; i++)
+                member_offsets[i] = parts[(size_t)i + f];
+    }
+    if (file_offsets)
+        file_offsets[bs.nfiles] = tot;
+    if (total)
+        *total = tot;
+    if (ms)
+        (void)hipEventElapsedTime(ms, bs.ev[0], bs.ev[1]);
+    return tot > bs.cap ? Z_BUF_ERROR : Z_OK;
 }
 
 /* ---- level 0 --------------------------------------------------------------------- */
@@ -5386,6 +5619,99 @@ extern "C" ZlibReturn zsc_hip_compress_batch_packed(U32 count, const U8 *sources
     }
     (void)hipDeviceSynchronize();
     for (DevBuf *b : {&d_img, &d_in, &d_out, &d_packed, &d_table, &d_lens, &d_slots})
+        b->release();
+    zsc_hip_deflate_plan_destroy(pl);
+    return rc;
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_compress_batch(U32 nfiles, const U8 *const *sources, const uint64_t *source_lens,
+                                                  U8 *const *dests, uint64_t *dest_lens, I32 *statuses, I32 level,
+                                                  I32 mem_level, ZlibStrategy strategy, U32 block_bytes)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(nfiles == 0 || (sources != Z_NULL && source_lens != Z_NULL && dests != Z_NULL && dest_lens != Z_NULL));
+    if (block_bytes == 0)
+        block_bytes = 65280u;
+    if (level == Z_NO_COMPRESSION || (block_bytes & 15u) || block_bytes > BZ_MAX_MEMBER)
+        return Z_STREAM_ERROR;
+    /* file f lies at base[f], a multiple of 16, and is cut where it lies: block_bytes is one too, so every
+     * buffer starts at one, and the plan compresses a buffer as if nothing lay before or behind it */
+    std::vector<uint64_t> base((size_t)nfiles + 1u, 0);
+    std::vector<U32> first((size_t)nfiles + 1u, 0);
+    for (U32 f = 0; f < nfiles; f++) {
+        const uint64_t nb = (source_lens[f] + block_bytes - 1u) / block_bytes;
+        if (source_lens[f] > (1ull << 46) || first[f] + nb > 0x7fffffffull - nfiles)
+            return Z_MEM_ERROR;
+        first[f + 1u] = first[f] + (U32)nb;
+        base[f + 1u] = base[f] + ((source_lens[f] + 15u) & ~15ull);
+    }
+    const U32 count = first[nfiles];
+    if (count == 0) { /* nothing to compress: every file is the 28 bytes that end one */
+        static const U8 kEof[BZ_TAIL] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0};
+        for (U32 f = 0; f < nfiles; f++) {
+            const bool room = dest_lens[f] >= BZ_TAIL;
+            if (room)
+                memcpy(dests[f], kEof, BZ_TAIL);
+            dest_lens[f] = BZ_TAIL;
+            if (statuses)
+                statuses[f] = room ? Z_OK : Z_BUF_ERROR;
+        }
+        return Z_OK;
+    }
+    std::vector<U32> lens(std::max<U32>(count, 1)), caps(std::max<U32>(count, 1));
+    std::vector<uint64_t> in_off(std::max<U32>(count, 1)), out_off(std::max<U32>(count, 1));
+    uint64_t out_bytes = 0;
+    for (U32 f = 0; f < nfiles; f++)
+        for (U32 i = first[f]; i < first[f + 1u]; i++) {
+            const uint64_t at = (uint64_t)(i - first[f]) * block_bytes;
+            lens[i] = (U32)std::min<uint64_t>(block_bytes, source_lens[f] - at);
+        }
+    ZlibReturn rc = zsc_hip_deflate_plan_layout(count, lens.data(), level, 31, mem_level, in_off.data(), out_off.data(),
+                                                caps.data(), Z_NULL, &out_bytes);
+    if (rc != Z_OK)
+        return rc;
+    for (U32 f = 0; f < nfiles; f++)
+        for (U32 i = first[f]; i < first[f + 1u]; i++)
+            in_off[i] = base[f] + (uint64_t)(i - first[f]) * block_bytes;
+    zsc_hip_deflate_plan *pl = nullptr;
+    rc = zsc_hip_deflate_plan_create(&pl, count, lens.data(), in_off.data(), out_off.data(), caps.data(), level, 31,
+                                     mem_level, strategy);
+    if (rc != Z_OK)
+        return rc;
+    rc = zsc_hip_deflate_plan_bgzf_enable(pl, nfiles, first.data(), 16u);
+    DevBuf d_in, d_out, d_image;
+    const uint64_t icap = rc == Z_OK ? pl->bgzf.max_total : 0;
+    if (rc == Z_OK && !(d_in.ensure(base[nfiles] + 64u) && d_out.ensure(out_bytes) && d_image.ensure(icap)))
+        rc = Z_MEM_ERROR;
+    for (U32 f = 0; rc == Z_OK && f < nfiles; f++) /* one copy in per file */
+        if (source_lens[f] && hipMemcpy((uint8_t *)d_in.p + base[f], sources[f], source_lens[f],
+                                        hipMemcpyHostToDevice) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_run(pl, d_in.p, d_out.p, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_bgzf(pl, d_out.p, d_image.p, icap, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_results(pl, Z_NULL, Z_NULL);
+    if (rc == Z_OK) {
+        std::vector<uint64_t> off((size_t)nfiles + 1u), flen(std::max<U32>(nfiles, 1));
+        std::vector<I32> fst(std::max<U32>(nfiles, 1));
+        rc = zsc_hip_deflate_plan_bgzf_results(pl, off.data(), flen.data(), fst.data(), Z_NULL, Z_NULL, Z_NULL);
+        for (U32 f = 0; rc == Z_OK && f < nfiles; f++) { /* ... and one out */
+            const uint64_t room = dest_lens[f];
+            dest_lens[f] = flen[f];
+            I32 s = fst[f];
+            if (s == Z_OK && flen[f] > room)
+                s = Z_BUF_ERROR;
+            else if (s == Z_OK &&
+                     hipMemcpy(dests[f], (const uint8_t *)d_image.p + off[f], flen[f], hipMemcpyDeviceToHost) != hipSuccess)
+                rc = Z_STREAM_ERROR;
+            if (statuses)
+                statuses[f] = s;
+        }
+    }
+    (void)hipDeviceSynchronize();
+    for (DevBuf *b : {&d_in, &d_out, &d_image})
         b->release();
     zsc_hip_deflate_plan_destroy(pl);
     return rc;
