@@ -829,6 +829,106 @@ ZlibReturn zsc_hip_bgzf_compress_batch(U32 nfiles, const U8 *const *sources, con
                                        U8 *const *dests, uint64_t *dest_lens, I32 *statuses, I32 level,
                                        I32 mem_level, ZlibStrategy strategy, U32 block_bytes);
 
+/* BGZF ranges ---------------------------------------------------------------
+ *
+ * BGZF's seek points are its member starts, and they cost no decode to find.  An INDEX keeps them for a batch
+ * of device-resident files; a RANGES plan decodes only the members its requests touch
+ * (zsc_amd/csrc/bgzf_read.h).  The counterpart of the seek-point indexes above, which
+ * give points INSIDE one stream.
+ *
+ * The index of a file of n bytes is the table of this walk:
+ *     at = 0; out = 0; k = 0
+ *     loop: the header at `at` must be a BGZF member's: 1f 8b 08, FEXTRA set and the reserved FLG bits clear, a
+ *           `B` `C` subfield of length 2 whose BSIZE + 1 = L keeps the member inside the file with room for the
+ *           extra field and a trailer, and an ISIZE (the last four bytes of those L) of at most 65 536; else stop
+ *           coffset[k] = at; uoffset[k] = out; k += 1;  at += L; out += ISIZE
+ *     coffset[k] = at; uoffset[k] = out                                                  (the end entry)
+ * members = k, indexed_bytes = at, total_out = out.  A file that is not BGZF has 0 members, which is no error;
+ * bytes behind the last member (padding, anything) are not indexed.  Nothing is decoded: the table is a set of
+ * claims, each verified when a range is read.  Files are up to 4 GiB - 1 long (U32, as in a members plan) at
+ * 16-byte aligned offsets with 64 readable bytes behind each; the tables are u64, as in .gzi.
+ *
+ * zsc_hip_bgzf_index_build is synchronous, like a plan's create: it enqueues on hip_stream a members plan's scan
+ *   and claims launches and a walk over the claims' links, waits, reads the counts back and keeps the exact table
+ *   on the device (every file's coffsets, then every file's uoffsets; no call hands it out yet) and on the host.
+ *   Its scratch is a members plan's plus 16 bytes per 26 bytes of input -- the room every file's table could need,
+ *   0.6 of the input -- all released before it returns; what it keeps is _scratch_bytes, 16 bytes per entry.
+ *   _build_ms: the device time of its launches up to the walk.  Z_MEM_ERROR where an allocation failed,
+ *   Z_STREAM_ERROR where a copy, a launch or the wait did; the same holds for _import_gzi.
+ * _info, _table (cap: the entries coffsets and uoffsets have room for; Z_BUF_ERROR below members + 1; either
+ *   may be NULL), _voffset and _uoffset need no device.  A virtual offset is coffset << 16 | offset within the
+ *   member.  _voffset gives the one of the member that HOLDS byte uoffset (never an empty member's), and for
+ *   total_out the end entry's with 0 within; Z_STREAM_ERROR beyond total_out.  _uoffset takes any virtual offset
+ *   whose compressed part is a member start of the table (or its end entry, with 0 within) and whose part within
+ *   is at most that member's length; Z_STREAM_ERROR otherwise.
+ * _export_gzi / _import_gzi: the .gzi layout of bgzip -r -- a little-endian u64 count, then (u64 compressed,
+ *   u64 uncompressed) for every member start after the first; the first member at (0, 0) is implicit and there
+ *   is no end entry.  No htslib was at hand: that a file bgzip wrote loads here rests on that published layout,
+ *   not on a test against one.  _export_gzi: *gzi_len is the room in, the length out (Z_BUF_ERROR where it does
+ *   not fit or gzi is NULL).  _import_gzi makes a one-file index from an image and the file on the device: every
+ *   entry is checked there, one per lane -- it must be a member start whose claim ends at the next entry with the
+ *   length the uncompressed offsets differ by -- and the walk goes on behind the last entry to the end entry.
+ *   Its room on the device is 16 bytes per named entry and per 26 bytes of the file behind the last named start.
+ *   An image that does not fit the file is Z_DATA_ERROR, so an imported index is exactly what _build gives for
+ *   that file, or it is refused.
+ *
+ * zsc_hip_inflate_plan_create_bgzf_ranges: item i asks for bytes [begins[i], begins[i] + lens[i]) of the
+ *   uncompressed content of file files[i], written to [dst_offsets[i], + dest_caps[i]) of the run's d_dst
+ *   (16-byte aligned offsets).  With ZSC_HIP_BGZF_VOFFSETS, begins[i] and lens[i] are a begin and an END virtual
+ *   offset, converted with _uoffset: Z_STREAM_ERROR where either is refused there or end < begin.  The plan
+ *   copies what it needs: the index may be destroyed before the run.  Create clips each range to total_out and
+ *   makes one job per member that contributes a byte, longest member first.  In a run a lane group takes a
+ *   job, evaluates the member's claim again -- it must give the index's end and length -- and decodes the member
+ *   with the plain decode, which must return Z_OK with exactly that length and consumed count.  A member the
+ *   range covers whole is decoded in place; an edge member (two per range at the most) goes whole into the
+ *   group's staging slot, and the group copies the slice out.  Per item, by _results:
+ *     Z_OK          dest_len is the clipped length (0 for a range at or behind total_out or of length 0: no job
+ *                   runs), consumed the compressed offset behind the last member decoded (0 if none); bytes of
+ *                   the destination behind dest_len are untouched
+ *     Z_BUF_ERROR   dest_caps[i] is below the clipped length: nothing is written, dest_len says what it takes
+ *     Z_DATA_ERROR  a job of the item was not good: dest_len and consumed are 0, the bytes in the item's own
+ *                   destination unspecified.  One damaged member fails only the requests that touch it.
+ *   Whatever the files or the index hold, nothing is written outside [dst_offsets[i], + dest_caps[i]) and the
+ *   staging slots, and nothing is read outside a file and the 64 bytes behind it.  Coordinates are the index's:
+ *   a member whose ISIZE field was altered shifts everything behind it, as for every BGZF reader.
+ *   _run, _results, _destroy, _scratch_bytes and _pack_enable / _pack (which packs the Z_OK items) work as on any
+ *   inflate plan; _index_enable and _dict_enable return Z_STREAM_ERROR; _results relaunches nothing.  Scratch:
+ *   40 bytes per job, 20 per request, 16 per file, and -- where the plan has an edge job -- 65 552 bytes of
+ *   staging for each lane group of the launch (four per wavefront, at most 20 wavefronts per CU, never more
+ *   wavefronts than jobs / 4), whatever the number of requests -- on an MI355X 20 480 slots, 1.34 GB, for any
+ *   plan of 81 920 jobs or more of which one is an edge; a plan of whole members has none.  That is beyond a
+ *   plain plan's own buffers (items, queue order, results, resume records: 72 bytes per request), which a ranges plan has as
+ *   well and _scratch_bytes does not count.  The environment variable ZSC_HIP_BGZF_GROUPS,
+ *   read at create, caps the lane groups (a test hook: staging slots are then reused by many jobs).
+ * _bgzf_jobs: the jobs of a ranges plan and the bytes they decode (either may be NULL).
+ * zsc_hip_bgzf_read_ranges_batch: host memory.  Every file goes up once, an index and a ranges plan are made,
+ *   and the Z_OK items come back as one packed image, dealt out to dests.  dest_lens[i]: in, the room at
+ *   dests[i]; out, the item's dest_len.  A process that calls none of these allocates and launches what it did. */
+#define ZSC_HIP_BGZF_VOFFSETS 1u
+typedef struct zsc_hip_bgzf_index zsc_hip_bgzf_index;
+ZlibReturn zsc_hip_bgzf_index_build(zsc_hip_bgzf_index **index, U32 nfiles, const void *d_src, const U32 *source_lens,
+                                    const uint64_t *src_offsets, void *hip_stream);
+ZlibReturn zsc_hip_bgzf_index_import_gzi(zsc_hip_bgzf_index **index, const U8 *gzi, uint64_t gzi_len,
+                                         const void *d_src, U32 source_len, uint64_t src_offset, void *hip_stream);
+ZlibReturn zsc_hip_bgzf_index_export_gzi(const zsc_hip_bgzf_index *index, U32 file, U8 *gzi, uint64_t *gzi_len);
+ZlibReturn zsc_hip_bgzf_index_info(const zsc_hip_bgzf_index *index, U32 file, U32 *members, uint64_t *indexed_bytes,
+                                   uint64_t *total_out);
+ZlibReturn zsc_hip_bgzf_index_table(const zsc_hip_bgzf_index *index, U32 file, uint64_t *coffsets, uint64_t *uoffsets,
+                                    U32 cap);
+ZlibReturn zsc_hip_bgzf_index_voffset(const zsc_hip_bgzf_index *index, U32 file, uint64_t uoffset, uint64_t *voffset);
+ZlibReturn zsc_hip_bgzf_index_uoffset(const zsc_hip_bgzf_index *index, U32 file, uint64_t voffset, uint64_t *uoffset);
+uint64_t zsc_hip_bgzf_index_scratch_bytes(const zsc_hip_bgzf_index *index);
+float zsc_hip_bgzf_index_build_ms(const zsc_hip_bgzf_index *index);
+void zsc_hip_bgzf_index_destroy(zsc_hip_bgzf_index *index);
+ZlibReturn zsc_hip_inflate_plan_create_bgzf_ranges(zsc_hip_inflate_plan **plan, const zsc_hip_bgzf_index *index,
+                                                   U32 count, const U32 *files, const uint64_t *begins,
+                                                   const uint64_t *lens, const U32 *dest_caps,
+                                                   const uint64_t *dst_offsets, U32 flags);
+ZlibReturn zsc_hip_inflate_plan_bgzf_jobs(zsc_hip_inflate_plan *plan, uint64_t *jobs, uint64_t *decoded_bytes);
+ZlibReturn zsc_hip_bgzf_read_ranges_batch(U32 nfiles, const U8 *const *sources, const U32 *source_lens, U32 count,
+                                          const U32 *files, const uint64_t *begins, const uint64_t *lens,
+                                          U8 *const *dests, U32 *dest_lens, I32 *statuses, U32 flags);
+
 /* preset dictionaries (decompression only) ---------------------------------
  *
  * zsc_hip_inflate_plan_dict_enable gives every stream of a PLAIN plan (zsc_hip_inflate_plan_create,

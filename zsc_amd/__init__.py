@@ -32,6 +32,9 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
   ``pack`` / ``pack_results``, the same on :class:`InflatePlan`);
 * :func:`bgzf_compress_batch` -- files written as BGZF, the block-gzip container of bgzip, BAM and tabix, which a
   members plan reads back member by member (``DeflatePlan.bgzf_enable`` / ``bgzf`` / ``bgzf_results``);
+* :class:`BgzfIndex`, :class:`BgzfRangesPlan` (``InflatePlan.bgzf_ranges``), :func:`bgzf_read_ranges` -- ranges read out
+  of BGZF files by uncompressed or virtual offset: a member index built from the headers alone (``to_gzi`` /
+  ``from_gzi``), and a plan that decodes only the members its requests touch;
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -52,6 +55,6 @@ from .api import (  # noqa: F401
     compress_batch_verified, VERIFY_OK, VERIFY_SKIPPED, VERIFY_HEADER, VERIFY_BLOCK_HDR, VERIFY_CODES, VERIFY_LITERAL,
     VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH, VERIFY_BIT_END, VERIFY_TRAILER,
     PACK_TILE, unpack, compress_batch_packed, uncompress_batch_packed, PackedCallError,
-    bgzf_compress_batch,
+    bgzf_compress_batch, BgzfIndex, BgzfRangesPlan, bgzf_read_ranges, BGZF_VOFFSETS,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

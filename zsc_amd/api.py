@@ -177,6 +177,25 @@ def _load() -> C.CDLL:
     L.zsc_hip_deflate_plan_bgzf_results.argtypes = [C.c_void_p, u64p, u64p, i32p, u64p, u64p, C.POINTER(C.c_float)]
     L.zsc_hip_bgzf_compress_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u64p, C.POINTER(C.c_void_p), u64p,
                                               i32p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
+    L.zsc_hip_bgzf_index_build.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, u32p, u64p, C.c_void_p]
+    L.zsc_hip_bgzf_index_import_gzi.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                C.c_uint64, C.c_void_p]
+    L.zsc_hip_bgzf_index_export_gzi.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, u64p]
+    L.zsc_hip_bgzf_index_info.argtypes = [C.c_void_p, C.c_uint32, u32p, u64p, u64p]
+    L.zsc_hip_bgzf_index_table.argtypes = [C.c_void_p, C.c_uint32, u64p, u64p, C.c_uint32]
+    L.zsc_hip_bgzf_index_voffset.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, u64p]
+    L.zsc_hip_bgzf_index_uoffset.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, u64p]
+    L.zsc_hip_bgzf_index_scratch_bytes.argtypes = [C.c_void_p]
+    L.zsc_hip_bgzf_index_scratch_bytes.restype = C.c_uint64
+    L.zsc_hip_bgzf_index_build_ms.argtypes = [C.c_void_p]
+    L.zsc_hip_bgzf_index_build_ms.restype = C.c_float
+    L.zsc_hip_bgzf_index_destroy.argtypes = [C.c_void_p]
+    L.zsc_hip_bgzf_index_destroy.restype = None
+    L.zsc_hip_inflate_plan_create_bgzf_ranges.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32, u32p, u64p,
+                                                          u64p, u32p, u64p, C.c_uint32]
+    L.zsc_hip_inflate_plan_bgzf_jobs.argtypes = [C.c_void_p, u64p, u64p]
+    L.zsc_hip_bgzf_read_ranges_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u32p, C.c_uint32, u32p, u64p, u64p,
+                                                 C.POINTER(C.c_void_p), u32p, i32p, C.c_uint32]
     L.zsc_hip_unpack.argtypes = [C.c_uint32, C.c_void_p, u64p, u32p, C.c_void_p, u64p, C.c_void_p]
     L.zsc_hip_compress_batch_packed.argtypes = [C.c_uint32, C.c_char_p, u64p, C.c_void_p, C.c_uint64, u64p, i32p,
                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
@@ -1051,6 +1070,190 @@ class InflatePlan(_Packing):
             self.close()
         except Exception:
             pass
+
+
+BGZF_VOFFSETS = 1
+
+
+class BgzfIndex:
+    """The member index of a batch of BGZF files on the device (zsc_hip_bgzf_index_build, include/zsc_hip.h
+    "BGZF ranges"): per file the compressed and uncompressed offset of every member start and of the end, found
+    from the headers alone.  d_src is the device pointer of the batch, file f at src_offsets[f] (multiples of 16,
+    64 readable bytes behind each; None: one behind the other as InflatePlan lays sources out, see src_offsets
+    and src_bytes).  A file that is not BGZF has 0 members."""
+
+    def __init__(self, d_src: int, source_lens: Sequence[int], src_offsets: Sequence[int] | None = None,
+                 stream: int = 0, _handle=None):
+        self.nfiles = n = len(source_lens)
+        self.source_lens = list(source_lens)
+        self.src_offsets, self.src_bytes = self.layout(source_lens) if src_offsets is None else (list(src_offsets), 0)
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+            return
+        rc = lib.zsc_hip_bgzf_index_build(C.byref(self._h), n, C.c_void_p(d_src), (C.c_uint32 * max(n, 1))(*source_lens),
+                                          (C.c_uint64 * max(n, 1))(*self.src_offsets), C.c_void_p(stream))
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_bgzf_index_build failed: {rc}")
+
+    @staticmethod
+    def layout(source_lens: Sequence[int]) -> Tuple[List[int], int]:
+        """(src_offsets, src_bytes) of files laid out one behind the other, as InflatePlan lays sources out"""
+        so, sb = [], 0
+        for sl in source_lens:
+            so.append(sb)
+            sb += (sl + 64 + 15) & ~15
+        return so, sb + 64
+
+    @classmethod
+    def from_gzi(cls, gzi: bytes, d_src: int, source_len: int, src_offset: int = 0, stream: int = 0) -> "BgzfIndex":
+        """A one-file index from a .gzi image (bgzip -r) and the file on the device.  Every entry is checked
+        against the file there; ValueError (Z_DATA_ERROR) where the image does not fit it, so what comes back is
+        exactly what building the index gives."""
+        h = C.c_void_p()
+        rc = lib.zsc_hip_bgzf_index_import_gzi(C.byref(h), gzi, len(gzi), C.c_void_p(d_src), source_len, src_offset,
+                                               C.c_void_p(stream))
+        if rc == Z_DATA_ERROR:
+            raise ValueError("the .gzi image does not fit the file")
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_bgzf_index_import_gzi failed: {rc}")
+        return cls(d_src, [source_len], [src_offset], _handle=h)
+
+    def info(self, file: int = 0) -> Tuple[int, int, int]:
+        """(members, indexed_bytes, total_out) of a file"""
+        m, ib, to = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        rc = lib.zsc_hip_bgzf_index_info(self._h, file, C.byref(m), C.byref(ib), C.byref(to))
+        if rc != Z_OK:
+            raise ValueError(f"zsc_hip_bgzf_index_info failed: {rc}")
+        return m.value, ib.value, to.value
+
+    def table(self, file: int = 0) -> Tuple[List[int], List[int]]:
+        """(coffsets, uoffsets) of a file: members + 1 entries each, the last the end entry"""
+        n = self.info(file)[0] + 1
+        c, u = (C.c_uint64 * n)(), (C.c_uint64 * n)()
+        rc = lib.zsc_hip_bgzf_index_table(self._h, file, c, u, n)
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_bgzf_index_table failed: {rc}")
+        return list(c), list(u)
+
+    def voffset(self, uoffset: int, file: int = 0) -> int:
+        """the virtual offset (coffset << 16 | offset within the member) of uncompressed offset uoffset"""
+        v = C.c_uint64()
+        if lib.zsc_hip_bgzf_index_voffset(self._h, file, uoffset, C.byref(v)) != Z_OK:
+            raise ValueError(f"uncompressed offset {uoffset} is beyond the end of file {file}")
+        return v.value
+
+    def uoffset(self, voffset: int, file: int = 0) -> int:
+        """the uncompressed offset of a virtual offset of the index"""
+        u = C.c_uint64()
+        if lib.zsc_hip_bgzf_index_uoffset(self._h, file, voffset, C.byref(u)) != Z_OK:
+            raise ValueError(f"virtual offset {voffset:#x} is not of the index of file {file}")
+        return u.value
+
+    def to_gzi(self, file: int = 0) -> bytes:
+        """the index of a file as a .gzi image"""
+        need = C.c_uint64(0)
+        lib.zsc_hip_bgzf_index_export_gzi(self._h, file, None, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        rc = lib.zsc_hip_bgzf_index_export_gzi(self._h, file, buf, C.byref(need))
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_bgzf_index_export_gzi failed: {rc}")
+        return buf.raw[:need.value]
+
+    def build_ms(self) -> float:
+        """device time of the build's launches"""
+        return float(lib.zsc_hip_bgzf_index_build_ms(self._h))
+
+    def scratch_bytes(self) -> int:
+        return int(lib.zsc_hip_bgzf_index_scratch_bytes(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            lib.zsc_hip_bgzf_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BgzfRangesPlan(InflatePlan):
+    """A ranges plan (zsc_hip_inflate_plan_create_bgzf_ranges): request i is bytes [begins[i], begins[i] + lens[i])
+    of the uncompressed content of file files[i] of the index, decoded from the members it touches alone into
+    [dst_offsets[i], + dest_caps[i]) of run()'s d_dst; d_src is the batch the index was built over.  With
+    voffsets=True begins and lens are begin and END virtual offsets (ValueError where one is not of the index).
+    run, results, pack_enable / pack, scratch_bytes and close are InflatePlan's; the index may be closed before
+    the run.  Also made by InflatePlan.bgzf_ranges(...)."""
+
+    def __init__(self, index: BgzfIndex, files: Sequence[int], begins: Sequence[int], lens: Sequence[int],
+                 dest_caps: Sequence[int], voffsets: bool = False, dst_offsets: Sequence[int] | None = None):
+        self.count = n = len(files)
+        if not (len(begins) == len(lens) == len(dest_caps) == n):
+            raise ValueError("one file, begin, length and capacity per request")
+        do, db = [], 0
+        for dc in dest_caps:
+            do.append(db)
+            db += (dc + 64 + 15) & ~15
+        if dst_offsets is not None:
+            do = list(dst_offsets)
+            db = max([o + c for o, c in zip(do, dest_caps)], default=0)
+        self.src_offsets, self.src_bytes = index.src_offsets, index.src_bytes
+        self.dst_offsets, self.dst_bytes = do, db + 64
+        self._h = C.c_void_p()
+        m = max(n, 1)
+        rc = lib.zsc_hip_inflate_plan_create_bgzf_ranges(C.byref(self._h), index._h, n, (C.c_uint32 * m)(*files),
+                                                         (C.c_uint64 * m)(*begins), (C.c_uint64 * m)(*lens),
+                                                         (C.c_uint32 * m)(*dest_caps), (C.c_uint64 * m)(*do),
+                                                         BGZF_VOFFSETS if voffsets else 0)
+        if rc == Z_STREAM_ERROR:
+            raise ValueError("a request names no file of the index, an offset that is not of it, or an end before its begin")
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_create_bgzf_ranges failed: {rc}")
+
+    def jobs(self) -> Tuple[int, int]:
+        """(member jobs of the plan, the bytes they decode in a run)"""
+        j, b = C.c_uint64(), C.c_uint64()
+        rc = lib.zsc_hip_inflate_plan_bgzf_jobs(self._h, C.byref(j), C.byref(b))
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_inflate_plan_bgzf_jobs failed: {rc}")
+        return j.value, b.value
+
+    def index_enable(self, enable: bool = True) -> int:
+        """(zsc_hip_inflate_plan_index_enable: Z_STREAM_ERROR on a ranges plan)"""
+        return lib.zsc_hip_inflate_plan_index_enable(self._h, 1 if enable else 0)
+
+
+InflatePlan.bgzf_ranges = staticmethod(BgzfRangesPlan)
+
+
+def bgzf_read_ranges(files: Sequence[bytes], requests: Sequence[Tuple[int, int, int]],
+                     dest_caps: Sequence[int] | None = None, voffsets: bool = False):
+    """zsc_hip_bgzf_read_ranges_batch: requests[i] = (file, begin, length) -- with voffsets=True (file, begin
+    virtual offset, end virtual offset) -- read out of BGZF files in host memory: one upload per file, an index, a
+    ranges plan, one download.  dest_caps: the room per request (None: the length asked for, capped at 4 GiB - 1;
+    needed with voffsets).  Returns (rc, [bytes], [dest_len], [status]); the bytes of a request that is not Z_OK
+    are empty."""
+    nf, n = len(files), len(requests)
+    if dest_caps is None:
+        if voffsets:
+            raise ValueError("dest_caps are needed with virtual offsets")
+        dest_caps = [min(r[2], 0xffffffff) for r in requests]
+    srcs = (C.c_char_p * max(nf, 1))(*files)
+    slen = (C.c_uint32 * max(nf, 1))(*[len(f) for f in files])
+    bufs = [C.create_string_buffer(max(c, 1)) for c in dest_caps]
+    dsts = (C.c_void_p * max(n, 1))(*[C.cast(b, C.c_void_p) for b in bufs])
+    dlen = (C.c_uint32 * max(n, 1))(*dest_caps)
+    stat = (C.c_int32 * max(n, 1))()
+    rc = lib.zsc_hip_bgzf_read_ranges_batch(nf, srcs, slen, n, (C.c_uint32 * max(n, 1))(*[r[0] for r in requests]),
+                                            (C.c_uint64 * max(n, 1))(*[r[1] for r in requests]),
+                                            (C.c_uint64 * max(n, 1))(*[r[2] for r in requests]), dsts, dlen, stat,
+                                            BGZF_VOFFSETS if voffsets else 0)
+    if rc != Z_OK:
+        return rc, [], [], []
+    outs = [bufs[i].raw[:dlen[i]] if stat[i] == Z_OK else b"" for i in range(n)]
+    return rc, outs, list(dlen)[:n], list(stat)[:n]
 
 
 class DeflatePlan(_Packing):

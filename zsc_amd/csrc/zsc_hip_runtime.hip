@@ -34,6 +34,7 @@
 #include "inflate_size.h"
 #include "inflate_check.h"
 #include "inflate_members.h"
+#include "bgzf_read.h"
 #include "deflate_index.h"
 #include "deflate_verify.h"
 #include "pack.h"
@@ -1094,6 +1095,53 @@ __global__ __launch_bounds__(64) void k_mem_serial(const uint8_t *__restrict__ s
         lds_all[grp].cktab = crc_table;
     for (uint32_t s = blockIdx.x * INF_PER_WAVE + grp; s < M.sp.count; s += gridDim.x * INF_PER_WAVE)
         mem_serial<SIZE>(M, src, dst, &lds_all[grp], &r[grp], &rs[grp], res, resume, s);
+}
+
+/* kernel 14 (bgzf_read.h): BGZF ranges.  The index: the members plan's scan, setup and claims launches as they
+ * are, then k_bgi_chain, a lane group per file, and k_bgi_gather, a wavefront per file, which moves the tables
+ * from the room a file might have needed to the room it needs.  A ranges plan: k_bgr_range, lane groups taking
+ * member jobs from one queue, each group with BGR_SLOT bytes of `stage`, and k_bgr_finish, a lane per request. */
+__global__ __launch_bounds__(64) void k_bgi_chain(const uint8_t *__restrict__ src, MemPlan M,
+                                                  const uint64_t *__restrict__ tbase, uint64_t *__restrict__ coff,
+                                                  uint64_t *__restrict__ uoff, uint32_t *__restrict__ members)
+{
+    for (uint32_t s = blockIdx.x * INF_PER_WAVE + (threadIdx.x & 63u) / INF_GROUP; s < M.sp.count;
+         s += gridDim.x * INF_PER_WAVE)
+        bgi_chain(M, src, s, coff + tbase[s], uoff + tbase[s], tbase[s + 1u] - tbase[s], &members[s]);
+}
+
+__global__ __launch_bounds__(64) void k_bgi_gather(const uint64_t *__restrict__ tbase, const uint64_t *__restrict__ first,
+                                                   const uint64_t *__restrict__ coff, const uint64_t *__restrict__ uoff,
+                                                   uint64_t *__restrict__ table, uint64_t total, uint32_t nfiles)
+{
+    for (uint32_t f = blockIdx.x; f < nfiles; f += gridDim.x) {
+        const uint64_t n = first[f + 1u] - first[f];
+        for (uint64_t k = threadIdx.x; k < n; k += 64u) {
+            table[first[f] + k] = coff[tbase[f] + k];
+            table[total + first[f] + k] = uoff[tbase[f] + k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INF_WAVES_EU, INF_WAVES_EU))) void k_bgr_range(
+    const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint8_t *__restrict__ stage, BgrPlan B)
+{
+    __shared__ InfLds lds_all[INF_PER_WAVE];
+    __shared__ InfResult r[INF_PER_WAVE];
+    __shared__ InfResume rs[INF_PER_WAVE];
+    __shared__ uint32_t crc_table[1][256];
+    const uint32_t grp = (threadIdx.x & 63u) / INF_GROUP;
+    if ((threadIdx.x & (INF_GROUP - 1u)) == 0)
+        lds_all[grp].cktab = crc_table;
+    bgr_worker(B, src, dst, stage + (uint64_t)(blockIdx.x * INF_PER_WAVE + grp) * BGR_SLOT, &lds_all[grp], &r[grp],
+               &rs[grp]);
+}
+
+__global__ __launch_bounds__(64) void k_bgr_finish(BgrPlan B, const InfResult *__restrict__ res0,
+                                                   InfResult *__restrict__ res)
+{
+    for (uint32_t i = blockIdx.x * 64u + threadIdx.x; i < B.count; i += gridDim.x * 64u)
+        bgr_finish(B, res0, res, i);
 }
 
 /* kernel 7 (inflate_chunks.h): any stream inflated in parallel from block starts found by trial, in
@@ -4141,7 +4189,7 @@ static uint32_t inflate_grid(uint32_t count)
 
 #include "inflate_plan_layout.h"
 
-enum InfPlanKind { INF_PLAIN, INF_SECTIONS, INF_RESYNC, INF_CHUNKS, INF_INDEXED, INF_SIZE, INF_CHECK, INF_MEMBERS };
+enum InfPlanKind { INF_PLAIN, INF_SECTIONS, INF_RESYNC, INF_CHUNKS, INF_INDEXED, INF_SIZE, INF_CHECK, INF_MEMBERS, INF_BGZF_RANGES };
 
 struct zsc_hip_inflate_plan {
     /* a device buffer of the plan: it cannot be declared without joining `owned`, which destroy releases */
@@ -4158,7 +4206,7 @@ struct zsc_hip_inflate_plan {
     }
     bool has_chunks() const { return kind == INF_CHUNKS || kind == INF_SIZE || kind == INF_CHECK; } /* cp and the chunk records */
     bool has_rings() const { return kind == INF_CHECK; }                             /* a ring per lane group, a value per stream */
-    bool counts_pieces() const { return kind != INF_PLAIN; } /* every other kind keeps d_nsec, a sections plan's */
+    bool counts_pieces() const { return kind != INF_PLAIN && kind != INF_BGZF_RANGES; } /* the others keep d_nsec, a sections plan's */
     uint32_t count = 0;
     int32_t window_bits = 15;
     Buf d_items{owned}, d_order{owned}, d_res{owned}, d_resume{owned}, d_pending{owned};
@@ -4178,6 +4226,12 @@ struct zsc_hip_inflate_plan {
     /* members plans (inflate_members.h; sections plans' buffers, scanned for another pattern, and this one) */
     MemPlan mp = {};
     Buf d_mfiles{owned};
+    /* BGZF ranges plans (bgzf_read.h): a plain plan's buffers (d_items for the packs, d_res, and d_resume and
+     * d_pending, which a run zeroes so that _results relaunches nothing) and none of the kinds' above; bgr_waves: wavefronts of k_bgr_range, with
+     * BGR_SLOT bytes of d_bstage for each lane group where the plan has an edge job */
+    BgrPlan bp = {};
+    uint32_t bgr_waves = 0;
+    Buf d_bfiles{owned}, d_bjobs{owned}, d_bbad{owned}, d_bq{owned}, d_bstage{owned}, d_bres0{owned};
     /* size plans (inflate_size.h; with chunks they use cp and the chunks plan's record buffers, never
      * d_ring, d_win or d_chain_ck) */
     bool size_ran = false;
@@ -4793,6 +4847,20 @@ static void mem_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst
         hipLaunchKernelGGL(k_mem_serial<false>, dim3(g.per_group), dim3(64), 0, st, src, (uint8_t *)d_dst, M, res, resume);
 }
 
+/* the launches of a BGZF ranges plan, all of its run: the member jobs, then a result per request */
+static ZlibReturn bgr_enqueue(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st)
+{
+    const BgrPlan &B = pl->bp;
+    HIP_TRY(hipMemsetAsync(pl->d_bbad.p, 0, 4ull * pl->count, st), return Z_STREAM_ERROR);
+    HIP_TRY(hipMemsetAsync(pl->d_bq.p, 0, 16, st), return Z_STREAM_ERROR);
+    if (B.njobs)
+        hipLaunchKernelGGL(k_bgr_range, dim3(pl->bgr_waves), dim3(64), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst,
+                           (uint8_t *)pl->d_bstage.p, B);
+    hipLaunchKernelGGL(k_bgr_finish, dim3(std::max(1u, std::min((pl->count + 63u) / 64u, (uint32_t)g_cus * 8u))),
+                       dim3(64), 0, st, B, (const InfResult *)pl->d_bres0.p, (InfResult *)pl->d_res.p);
+    return Z_OK;
+}
+
 /* the whole-stream decode of what the launches above left: the first launch of a run, and every relaunch of
  * _results.  A check plan's first launch decodes into the rings; its relaunches are the size decode. */
 static void inflate_launch(zsc_hip_inflate_plan *pl, const void *d_src, void *d_dst, hipStream_t st, bool first)
@@ -4860,7 +4928,10 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_run(zsc_hip_inflate_plan *pl, const v
         chk_enqueue(pl, d_src, d_dst, st);
     if (pl->kind == INF_INDEXED && idx_enqueue(pl, d_src, d_dst, st) != Z_OK)
         return Z_STREAM_ERROR;
-    if (pl->kind == INF_MEMBERS)
+    if (pl->kind == INF_BGZF_RANGES) {
+        if (bgr_enqueue(pl, d_src, d_dst, st) != Z_OK)
+            return Z_STREAM_ERROR;
+    } else if (pl->kind == INF_MEMBERS)
         mem_enqueue(pl, d_src, d_dst, st); /* (its serial step is its whole-stream decode: nothing is relaunched) */
     else
         inflate_launch(pl, d_src, d_dst, st, true);
@@ -5460,7 +5531,10 @@ extern "C" ZlibReturn zsc_hip_inflate_plan_pack(zsc_hip_inflate_plan *pl, const 
     ZSC_ASSERT(pl != Z_NULL);
     /* the bytes written, whatever the status: what a damaged stream gave is kept */
     const PkLens lens = {(const uint32_t *)pl->d_res.p, 4u, 1u, PK_NO_STATUS};
-    return pack_enqueue(pl->pack, lens, d_output, d_packed, packed_cap, (hipStream_t)hip_stream);
+    /* (of a ranges plan the bytes of the Z_OK requests: another status wrote nothing it stands for) */
+    const PkLens ok_lens = {(const uint32_t *)pl->d_res.p, 4u, 1u, 0u};
+    return pack_enqueue(pl->pack, pl->kind == INF_BGZF_RANGES ? ok_lens : lens, d_output, d_packed, packed_cap,
+                        (hipStream_t)hip_stream);
 }
 
 extern "C" ZlibReturn zsc_hip_inflate_plan_pack_results(zsc_hip_inflate_plan *pl, uint64_t *offsets, uint64_t *total,
@@ -5785,5 +5859,453 @@ extern "C" ZlibReturn zsc_hip_uncompress_batch_packed(U32 count, const U8 *sourc
     for (DevBuf *b : {&d_img, &d_src, &d_dst, &d_packed, &d_table, &d_lens, &d_slots})
         b->release();
     zsc_hip_inflate_plan_destroy(pl);
+    return rc;
+}
+
+/* ---- BGZF ranges: the member index and the ranges plan (bgzf_read.h, bgzf_read_host.h) ------------------ */
+
+#include "bgzf_read_host.h"
+
+struct zsc_hip_bgzf_index {
+    uint32_t nfiles = 0;
+    std::vector<BgrFile> files;
+    std::vector<uint64_t> first; /* nfiles + 1: where a file's members + 1 entries start in the tables */
+    std::vector<uint64_t> coff, uoff;
+    DevBuf d_table;              /* the same on the device: every coffset, then every uoffset */
+    float build_ms = 0.f;
+
+    BgzTable table(uint32_t f) const
+    {
+        return {coff.data() + first[f], uoff.data() + first[f], (uint32_t)(first[f + 1] - first[f] - 1u)};
+    }
+};
+
+extern "C" void zsc_hip_bgzf_index_destroy(zsc_hip_bgzf_index *ix)
+{
+    DeviceScope scope;
+    if (!ix)
+        return;
+    ix->d_table.release();
+    delete ix;
+}
+
+/* the tables of an index whose `first` is set, from the device (every coffset, then every uoffset) */
+static bool bgi_download(zsc_hip_bgzf_index *ix)
+{
+    const uint64_t total = ix->first[ix->nfiles];
+    ix->coff.resize(total);
+    ix->uoff.resize(total);
+    return hipMemcpy(ix->coff.data(), ix->d_table.p, 8 * total, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(ix->uoff.data(), (const uint64_t *)ix->d_table.p + total, 8 * total, hipMemcpyDeviceToHost) ==
+               hipSuccess;
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_index_build(zsc_hip_bgzf_index **index_out, U32 nfiles, const void *d_src,
+                                               const U32 *source_lens, const uint64_t *src_offsets, void *hip_stream)
+{
+    ZSC_ASSERT(index_out != Z_NULL);
+    *index_out = nullptr;
+    ZSC_ASSERT(nfiles == 0 || (source_lens != Z_NULL && src_offsets != Z_NULL));
+    /* the buffers, the layout and the view of a members plan over the files: its first four launches are the
+     * index's (claims on, whatever the plan's switch says) */
+    std::vector<U32> caps(nfiles, 0);
+    std::vector<uint64_t> zero(nfiles, 0);
+    zsc_hip_inflate_plan *mp = nullptr;
+    ZlibReturn rc = zsc_hip_inflate_plan_create_members(&mp, nfiles, source_lens, src_offsets, caps.data(), zero.data(),
+                                                        31, 0);
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    mp->mp.claims = 1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto *ix = new zsc_hip_bgzf_index();
+    ix->nfiles = nfiles;
+    ix->files.resize(nfiles);
+    ix->first.assign(nfiles + 1ull, 0);
+    std::vector<uint64_t> tbase(nfiles + 1ull, 0);
+    for (U32 f = 0; f < nfiles; f++) {
+        ix->files[f] = BgrFile{src_offsets[f], source_lens[f], 0};
+        tbase[f + 1] = tbase[f] + BGI_TABLE_CAP(source_lens[f]);
+    }
+    DevBuf d_tbase, d_first, d_coff, d_uoff, d_members;
+    std::vector<U32> members(nfiles);
+    /* (mem: every allocation was had -- what failed otherwise was a copy, a launch or the wait) */
+    bool mem = d_tbase.ensure(8 * (nfiles + 1ull)) && d_first.ensure(8 * (nfiles + 1ull)) &&
+               d_coff.ensure(8 * std::max<uint64_t>(1, tbase[nfiles])) &&
+               d_uoff.ensure(8 * std::max<uint64_t>(1, tbase[nfiles])) && d_members.ensure(4 * std::max(1u, nfiles));
+    bool ok = mem && hipMemcpy(d_tbase.p, tbase.data(), 8 * (nfiles + 1ull), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && nfiles) {
+        const MemPlan &M = mp->mp;
+        const uint8_t *src = (const uint8_t *)d_src;
+        const InfGrid g(nfiles, mp->ncand_total, M.sp.ntiles);
+        (void)hipGetLastError();
+        ok = hipMemsetAsync(mp->d_scount.p, 0, 4ull * nfiles, st) == hipSuccess &&
+             hipMemsetAsync(mp->d_q.p, 0, 16, st) == hipSuccess;
+        (void)hipEventRecord(mp->ev0, st);
+        hipLaunchKernelGGL(k_mem_scan, dim3(g.scans), dim3(64), 0, st, src, M, 0);
+        hipLaunchKernelGGL(k_sec_setup, dim3(g.per_stream), dim3(64), 0, st, M.sp);
+        hipLaunchKernelGGL(k_mem_scan, dim3(g.scans), dim3(64), 0, st, src, M, 1);
+        hipLaunchKernelGGL(k_mem_claims, dim3(g.per_stream), dim3(64), 0, st, src, M);
+        hipLaunchKernelGGL(k_bgi_chain, dim3(g.per_group), dim3(64), 0, st, src, M, (const uint64_t *)d_tbase.p,
+                           (uint64_t *)d_coff.p, (uint64_t *)d_uoff.p, (uint32_t *)d_members.p);
+        (void)hipEventRecord(mp->ev1, st);
+        /* the counts come back, and the tables move to the room they need */
+        ok = ok && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess &&
+             hipMemcpy(members.data(), d_members.p, 4ull * nfiles, hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok)
+            (void)hipEventElapsedTime(&ix->build_ms, mp->ev0, mp->ev1);
+    }
+    for (U32 f = 0; ok && f < nfiles; f++)
+        ix->first[f + 1] = ix->first[f] + members[f] + 1ull;
+    const uint64_t total = ix->first[nfiles];
+    if (ok && !ix->d_table.ensure(16 * std::max<uint64_t>(1, total)))
+        ok = mem = false;
+    if (ok && nfiles) {
+        ok = hipMemcpyAsync(d_first.p, ix->first.data(), 8 * (nfiles + 1ull), hipMemcpyHostToDevice, st) == hipSuccess;
+        hipLaunchKernelGGL(k_bgi_gather, dim3(std::min(nfiles, (uint32_t)g_cus * 8u)), dim3(64), 0, st,
+                           (const uint64_t *)d_tbase.p, (const uint64_t *)d_first.p, (const uint64_t *)d_coff.p,
+                           (const uint64_t *)d_uoff.p, (uint64_t *)ix->d_table.p, total, nfiles);
+        ok = ok && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess && bgi_download(ix);
+    }
+    if (!ok) {
+        (void)hipStreamSynchronize(st); /* (what was enqueued before the failure may still use the buffers) */
+        (void)hipGetLastError();
+    }
+    for (DevBuf *b : {&d_tbase, &d_first, &d_coff, &d_uoff, &d_members})
+        b->release();
+    zsc_hip_inflate_plan_destroy(mp);
+    if (!ok) {
+        zsc_hip_bgzf_index_destroy(ix);
+        return mem ? Z_STREAM_ERROR : Z_MEM_ERROR;
+    }
+    *index_out = ix;
+    return Z_OK;
+}
+
+__global__ __launch_bounds__(64) void k_bgi_verify(const uint8_t *__restrict__ src, uint32_t n,
+                                                   const uint64_t *__restrict__ coff, const uint64_t *__restrict__ uoff,
+                                                   uint32_t cnt, uint32_t *__restrict__ out)
+{
+    for (uint32_t e0 = blockIdx.x * 64u; e0 < cnt; e0 += gridDim.x * 64u)
+        bgi_verify(src, n, coff, uoff, cnt, e0, out);
+}
+
+/* (one lane group: the walk behind the last named member start, over that entry) */
+__global__ __launch_bounds__(INF_GROUP) void k_bgi_tail(const uint8_t *__restrict__ src, uint32_t n, uint64_t *coff,
+                                                        uint64_t *uoff, uint32_t cnt, uint64_t tcap, uint32_t *out)
+{
+    const uint64_t at = coff[cnt - 1u];
+    if (at <= n)
+        bgi_walk(src, n, (uint32_t)at, uoff[cnt - 1u], coff + (cnt - 1u), uoff + (cnt - 1u), tcap - (cnt - 1u), out + 1);
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_index_import_gzi(zsc_hip_bgzf_index **index_out, const U8 *gzi, uint64_t gzi_len,
+                                                    const void *d_src, U32 source_len, uint64_t src_offset,
+                                                    void *hip_stream)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(index_out != Z_NULL);
+    *index_out = nullptr;
+    if (zsc_hip_init(-1) != Z_OK || (src_offset & 15u))
+        return Z_STREAM_ERROR;
+    std::vector<uint64_t> c, u;
+    if (gzi == Z_NULL || !bgz_gzi_parse(gzi, gzi_len, c, u) || c.size() + 1u > BGI_TABLE_CAP(source_len))
+        return Z_DATA_ERROR;
+    const uint32_t cnt = (uint32_t)c.size();
+    const uint64_t tcap = bgz_import_room(c, source_len);
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto *ix = new zsc_hip_bgzf_index();
+    ix->nfiles = 1;
+    ix->files.assign(1, BgrFile{src_offset, source_len, 0});
+    /* the table's room on the device: the named entries and what the walk behind the last of them can find
+     * (bgz_import_room); out[0]: an entry does not fit
+     * the file, out[1]: the members the walk found from the last entry on */
+    DevBuf d_out;
+    uint32_t out[2] = {0, 0};
+    const uint8_t *src = (const uint8_t *)d_src + src_offset;
+    uint64_t *dc = nullptr, *du = nullptr;
+    bool mem = ix->d_table.ensure(16 * tcap) && d_out.ensure(8), ok = mem;
+    if (ok) {
+        dc = (uint64_t *)ix->d_table.p;
+        du = dc + tcap;
+        (void)hipGetLastError();
+        ok = hipMemsetAsync(d_out.p, 0, 8, st) == hipSuccess &&
+             hipMemcpyAsync(dc, c.data(), 8ull * cnt, hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(du, u.data(), 8ull * cnt, hipMemcpyHostToDevice, st) == hipSuccess;
+        hipLaunchKernelGGL(k_bgi_verify, dim3(std::min((cnt + 63u) / 64u, (uint32_t)g_cus * 8u)), dim3(64), 0, st, src,
+                           source_len, (const uint64_t *)dc, (const uint64_t *)du, cnt, (uint32_t *)d_out.p);
+        hipLaunchKernelGGL(k_bgi_tail, dim3(1), dim3(INF_GROUP), 0, st, src, source_len, dc, du, cnt, tcap,
+                           (uint32_t *)d_out.p);
+        ok = ok && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess &&
+             hipMemcpy(out, d_out.p, 8, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipStreamSynchronize(st); /* (what was enqueued before the failure may still use the buffers) */
+        (void)hipGetLastError();
+    }
+    d_out.release();
+    ZlibReturn rc = !ok ? (mem ? Z_STREAM_ERROR : Z_MEM_ERROR) : out[0] ? Z_DATA_ERROR : Z_OK;
+    if (rc == Z_OK) {
+        /* (the uoffsets move up behind the coffsets: the layout of a built index) */
+        const uint64_t total = cnt + (uint64_t)out[1];
+        ix->first = {0, total};
+        ix->coff.resize(total);
+        ix->uoff.resize(total);
+        DevBuf exact;
+        mem = exact.ensure(16 * total);
+        ok = mem && hipMemcpy(exact.p, dc, 8 * total, hipMemcpyDeviceToDevice) == hipSuccess &&
+             hipMemcpy((uint64_t *)exact.p + total, du, 8 * total, hipMemcpyDeviceToDevice) == hipSuccess;
+        ix->d_table.release();
+        ix->d_table = exact;
+        ok = ok && bgi_download(ix);
+        rc = ok ? Z_OK : mem ? Z_STREAM_ERROR : Z_MEM_ERROR;
+    }
+    if (rc != Z_OK) {
+        zsc_hip_bgzf_index_destroy(ix);
+        return rc;
+    }
+    *index_out = ix;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_index_info(const zsc_hip_bgzf_index *ix, U32 file, U32 *members,
+                                              uint64_t *indexed_bytes, uint64_t *total_out)
+{
+    ZSC_ASSERT(ix != Z_NULL);
+    if (file >= ix->nfiles)
+        return Z_STREAM_ERROR;
+    const BgzTable T = ix->table(file);
+    if (members)
+        *members = T.members;
+    if (indexed_bytes)
+        *indexed_bytes = T.coff[T.members];
+    if (total_out)
+        *total_out = T.total_out();
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_index_table(const zsc_hip_bgzf_index *ix, U32 file, uint64_t *coffsets,
+                                               uint64_t *uoffsets, U32 cap)
+{
+    ZSC_ASSERT(ix != Z_NULL);
+    if (file >= ix->nfiles)
+        return Z_STREAM_ERROR;
+    const BgzTable T = ix->table(file);
+    if (cap < T.members + 1u)
+        return Z_BUF_ERROR;
+    if (coffsets)
+        std::copy(T.coff, T.coff + T.members + 1u, coffsets);
+    if (uoffsets)
+        std::copy(T.uoff, T.uoff + T.members + 1u, uoffsets);
+    return Z_OK;
+}
+
+extern "C" uint64_t zsc_hip_bgzf_index_scratch_bytes(const zsc_hip_bgzf_index *ix)
+{
+    return ix ? 16 * std::max<uint64_t>(1, ix->first[ix->nfiles]) : 0;
+}
+
+extern "C" float zsc_hip_bgzf_index_build_ms(const zsc_hip_bgzf_index *ix)
+{
+    return ix ? ix->build_ms : 0.f;
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_index_voffset(const zsc_hip_bgzf_index *ix, U32 file, uint64_t uoffset,
+                                                 uint64_t *voffset)
+{
+    ZSC_ASSERT(ix != Z_NULL);
+    ZSC_ASSERT(voffset != Z_NULL);
+    return file < ix->nfiles && bgz_voffset(ix->table(file), uoffset, voffset) ? Z_OK : Z_STREAM_ERROR;
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_index_uoffset(const zsc_hip_bgzf_index *ix, U32 file, uint64_t voffset,
+                                                 uint64_t *uoffset)
+{
+    ZSC_ASSERT(ix != Z_NULL);
+    ZSC_ASSERT(uoffset != Z_NULL);
+    return file < ix->nfiles && bgz_uoffset(ix->table(file), voffset, uoffset) ? Z_OK : Z_STREAM_ERROR;
+}
+
+extern "C" ZlibReturn zsc_hip_bgzf_index_export_gzi(const zsc_hip_bgzf_index *ix, U32 file, U8 *gzi, uint64_t *gzi_len)
+{
+    ZSC_ASSERT(ix != Z_NULL);
+    ZSC_ASSERT(gzi_len != Z_NULL);
+    if (file >= ix->nfiles)
+        return Z_STREAM_ERROR;
+    const BgzTable T = ix->table(file);
+    const uint64_t room = *gzi_len;
+    *gzi_len = bgz_gzi_bytes(T.members);
+    if (gzi == Z_NULL || room < *gzi_len)
+        return Z_BUF_ERROR;
+    bgz_gzi_export(T, gzi);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_create_bgzf_ranges(zsc_hip_inflate_plan **plan_out,
+                                                              const zsc_hip_bgzf_index *ix, U32 count, const U32 *files,
+                                                              const uint64_t *begins, const uint64_t *lens,
+                                                              const U32 *dest_caps, const uint64_t *dst_offsets,
+                                                              U32 flags)
+{
+    ZSC_ASSERT(plan_out != Z_NULL);
+    *plan_out = nullptr;
+    if (ix == Z_NULL || (flags & ~(U32)ZSC_HIP_BGZF_VOFFSETS) ||
+        (count && (files == Z_NULL || begins == Z_NULL || lens == Z_NULL || dest_caps == Z_NULL || dst_offsets == Z_NULL)))
+        return Z_STREAM_ERROR;
+    /* the requests cut into member jobs on the host, before anything is allocated */
+    std::vector<BgrJob> jobs;
+    std::vector<InfResult> res0(std::max(1u, count));
+    std::vector<U32> slen(count);
+    std::vector<uint64_t> soff(count);
+    uint64_t edges = 0;
+    for (U32 i = 0; i < count; i++) {
+        if (files[i] >= ix->nfiles) {
+            ZSC_WARN1("zsc_hip: request %u names a file the index does not have.", i);
+            return Z_STREAM_ERROR;
+        }
+        const BgzTable T = ix->table(files[i]);
+        uint64_t b = begins[i], n = lens[i];
+        if ((flags & ZSC_HIP_BGZF_VOFFSETS) && !bgr_from_voffsets(T, begins[i], lens[i], &b, &n)) {
+            ZSC_WARN1("zsc_hip: the virtual offsets of request %u are not of the index.", i);
+            return Z_STREAM_ERROR;
+        }
+        bgr_cut(T, files[i], i, b, n, dest_caps[i], dst_offsets[i], jobs, res0[i], &edges);
+        slen[i] = ix->files[files[i]].src_len;
+        soff[i] = ix->files[files[i]].src_off;
+    }
+    if (jobs.size() >= 0xffffffffull)
+        return Z_MEM_ERROR;
+    bgr_order(jobs);
+    ZlibReturn rc = zsc_hip_inflate_plan_create(plan_out, count, slen.data(), soff.data(), dest_caps, dst_offsets, 31);
+    if (rc != Z_OK)
+        return rc;
+    DeviceScope scope;
+    zsc_hip_inflate_plan *pl = *plan_out;
+    pl->kind = INF_BGZF_RANGES;
+    /* ZSC_HIP_BGZF_GROUPS (a test hook): fewer lane groups, so that every staging slot is reused by several jobs */
+    pl->bgr_waves = inflate_grid((uint32_t)jobs.size());
+    if (const char *e = getenv("ZSC_HIP_BGZF_GROUPS")) {
+        const long long g = atoll(e);
+        if (g > 0)
+            pl->bgr_waves = (uint32_t)std::min<long long>(pl->bgr_waves, (g + INF_PER_WAVE - 1) / INF_PER_WAVE);
+    }
+    const uint64_t nc = std::max(1u, count), nj = std::max<uint64_t>(1, jobs.size());
+    bool ok = pl->scratch(pl->d_bfiles, sizeof(BgrFile) * std::max(1u, ix->nfiles)) &&
+              pl->scratch(pl->d_bjobs, sizeof(BgrJob) * nj) && pl->scratch(pl->d_bbad, 4 * nc) &&
+              pl->scratch(pl->d_bq, 16) && pl->scratch(pl->d_bres0, sizeof(InfResult) * nc) &&
+              (edges == 0 || pl->scratch(pl->d_bstage, (uint64_t)BGR_SLOT * pl->bgr_waves * INF_PER_WAVE));
+    ok = ok && hipMemcpy(pl->d_bres0.p, res0.data(), sizeof(InfResult) * nc, hipMemcpyHostToDevice) == hipSuccess &&
+         (ix->nfiles == 0 || hipMemcpy(pl->d_bfiles.p, ix->files.data(), sizeof(BgrFile) * ix->nfiles,
+                                       hipMemcpyHostToDevice) == hipSuccess) &&
+         (jobs.empty() || hipMemcpy(pl->d_bjobs.p, jobs.data(), sizeof(BgrJob) * jobs.size(), hipMemcpyHostToDevice) ==
+                              hipSuccess);
+    if (!ok)
+        return inflate_plan_fail(plan_out);
+    BgrPlan &B = pl->bp;
+    B.files = (const BgrFile *)pl->d_bfiles.p;
+    B.jobs = (const BgrJob *)pl->d_bjobs.p;
+    B.bad = (uint32_t *)pl->d_bbad.p;
+    B.q = (uint32_t *)pl->d_bq.p;
+    B.njobs = (uint32_t)jobs.size();
+    B.count = count;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_inflate_plan_bgzf_jobs(zsc_hip_inflate_plan *pl, uint64_t *jobs, uint64_t *decoded_bytes)
+{
+    ZSC_ASSERT(pl != Z_NULL);
+    if (pl->kind != INF_BGZF_RANGES)
+        return Z_STREAM_ERROR;
+    std::vector<BgrJob> j(pl->bp.njobs);
+    DeviceScope scope;
+    if (!j.empty())
+        HIP_TRY(hipMemcpy(j.data(), pl->d_bjobs.p, sizeof(BgrJob) * j.size(), hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    uint64_t sum = 0;
+    for (const BgrJob &x : j)
+        sum += x.len;
+    if (jobs)
+        *jobs = j.size();
+    if (decoded_bytes)
+        *decoded_bytes = sum;
+    return Z_OK;
+}
+
+/* Host memory: the files go up once each, an index and a ranges plan are made over them, and the requests'
+ * bytes come back as one packed image that is dealt out to dests */
+extern "C" ZlibReturn zsc_hip_bgzf_read_ranges_batch(U32 nfiles, const U8 *const *sources, const U32 *source_lens,
+                                                     U32 count, const U32 *files, const uint64_t *begins,
+                                                     const uint64_t *lens, U8 *const *dests, U32 *dest_lens,
+                                                     I32 *statuses, U32 flags)
+{
+    DeviceScope scope;
+    if (count == 0)
+        return Z_OK;
+    ZSC_ASSERT(nfiles == 0 || (sources != Z_NULL && source_lens != Z_NULL));
+    ZSC_ASSERT(dests != Z_NULL);
+    ZSC_ASSERT(dest_lens != Z_NULL);
+    if (zsc_hip_init(-1) != Z_OK)
+        return Z_STREAM_ERROR;
+    std::vector<uint64_t> so(nfiles), dof(count), offs(count + 1ull);
+    uint64_t sb = 0, db = 0;
+    for (U32 f = 0; f < nfiles; f++) {
+        so[f] = sb;
+        sb += ((uint64_t)source_lens[f] + 64u + 15u) & ~15ull;
+    }
+    for (U32 i = 0; i < count; i++) {
+        dof[i] = db;
+        db += ((uint64_t)dest_lens[i] + 15u) & ~15ull;
+    }
+    DevBuf d_src, d_dst, d_packed;
+    zsc_hip_bgzf_index *ix = nullptr;
+    zsc_hip_inflate_plan *pl = nullptr;
+    ZlibReturn rc = d_src.ensure(sb + 64) ? Z_OK : Z_MEM_ERROR;
+    for (U32 f = 0; f < nfiles && rc == Z_OK; f++) {
+        ZSC_ASSERT(sources[f] != Z_NULL);
+        if (source_lens[f] &&
+            hipMemcpy((uint8_t *)d_src.p + so[f], sources[f], source_lens[f], hipMemcpyHostToDevice) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    if (rc == Z_OK)
+        rc = zsc_hip_bgzf_index_build(&ix, nfiles, d_src.p, source_lens, so.data(), nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_create_bgzf_ranges(&pl, ix, count, files, begins, lens, dest_lens, dof.data(), flags);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_pack_enable(pl, 1);
+    uint64_t pcap = 0;
+    if (rc == Z_OK) {
+        pcap = pl->pack.max_total;
+        if (!d_dst.ensure(db + 64) || !d_packed.ensure(pcap + 16))
+            rc = Z_MEM_ERROR;
+    }
+    std::vector<U32> outl(count);
+    std::vector<I32> stat(count);
+    std::vector<uint8_t> image;
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_run(pl, d_src.p, d_dst.p, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_results(pl, outl.data(), nullptr, stat.data(), nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_inflate_plan_pack(pl, d_dst.p, d_packed.p, pcap, nullptr);
+    if (rc == Z_OK) {
+        uint64_t total = 0;
+        rc = zsc_hip_inflate_plan_pack_results(pl, offs.data(), &total, Z_NULL);
+        image.resize(total);
+        if (rc == Z_OK && total && hipMemcpy(image.data(), d_packed.p, total, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    for (U32 i = 0; i < count && rc == Z_OK; i++) {
+        if (stat[i] == Z_OK && outl[i]) {
+            ZSC_ASSERT(dests[i] != Z_NULL);
+            memcpy(dests[i], image.data() + offs[i], outl[i]);
+        }
+        dest_lens[i] = outl[i];
+        if (statuses)
+            statuses[i] = stat[i];
+    }
+    (void)hipDeviceSynchronize();
+    for (DevBuf *b : {&d_src, &d_dst, &d_packed})
+        b->release();
+    zsc_hip_inflate_plan_destroy(pl);
+    zsc_hip_bgzf_index_destroy(ix);
     return rc;
 }
