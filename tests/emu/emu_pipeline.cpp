@@ -54,13 +54,9 @@ static inline void sg_count(int what, unsigned n)
 #include "../../zsc_amd/csrc/checksum.h"
 #include "../../zsc_amd/csrc/inflate.h"
 #include "../../zsc_amd/csrc/sections.h"
+#include "../../zsc_amd/csrc/deflate_plan_layout.h"
 #include <cstdio>
 #include <cstdlib>
-
-static const ZdLevel kLevels[10] = {
-    {0, 0, 0, 0, 0},       {4, 4, 8, 4, 0},       {4, 5, 16, 8, 0},     {4, 6, 32, 32, 0},
-    {4, 4, 16, 16, 1},     {8, 16, 32, 32, 1},    {8, 16, 128, 128, 1}, {8, 32, 128, 256, 1},
-    {32, 128, 258, 1024, 1}, {32, 258, 258, 4096, 1}};
 
 static int g_wbits = 15, g_mem_level = 8; /* emu_set_params: the window_bits / mem_level of the next calls */
 extern "C" void emu_set_params(int wbits, int mem_level)
@@ -68,15 +64,7 @@ extern "C" void emu_set_params(int wbits, int mem_level)
     g_wbits = wbits;
     g_mem_level = mem_level;
 }
-static ZdLevel level_cfg(int level)
-{
-    ZdLevel c = kLevels[level];
-    c.wsize = 1u << g_wbits;
-    c.max_dist = c.wsize - ZD_MIN_LOOKAHEAD;
-    c.sym_cap = (1u << (g_mem_level + 6)) - 1u;
-    c.hbits = (uint32_t)g_mem_level + 7u;
-    return c;
-}
+static ZdLevel level_cfg(int level) { return dpl_level(level, g_wbits, g_mem_level); }
 
 struct EmuChains {
     std::vector<uint8_t> in;
@@ -349,7 +337,7 @@ static void run_parse(const LzJob &job)
         return;
     }
     if (job.cfg.slow && (job.nsched == 0 || g_job_seg_ok) &&
-        (g_seg_mode >= 2 || (g_seg_mode == 0 && job.n > 18432u))) {
+        (g_seg_mode >= 2 || (g_seg_mode == 0 && dpl_ring_class(job.n) == 0))) {
         run_parse_seg(job, g_seg_mode == 3 ? 3 : 2);
         return;
     }
@@ -362,23 +350,16 @@ static void run_parse(const LzJob &job)
         lz_parse_lazy<LT>(job, lds);                 \
         free(lds);                                   \
     } while (0)
-        if (job.nsched) {
-            if (job.n > 18432u)
-                EMU_LAZY(LzLdsJ);
-            else if (job.n > 10240u)
-                EMU_LAZY(LzLdsJ16k);
-            else if (job.n > 6144u)
-                EMU_LAZY(LzLdsJ8k);
-            else
-                EMU_LAZY(LzLdsJ4k);
-        } else if (job.n > 18432u)
-            EMU_LAZY(LzLds);
-        else if (job.n > 10240u)
-            EMU_LAZY(LzLds16k);
-        else if (job.n > 6144u)
-            EMU_LAZY(LzLds8k);
-        else
-            EMU_LAZY(LzLds4k);
+        switch (dpl_ring_class(job.n) + (job.nsched ? 4 : 0)) {
+        case 0: EMU_LAZY(LzLds); break;
+        case 1: EMU_LAZY(LzLds16k); break;
+        case 2: EMU_LAZY(LzLds8k); break;
+        case 3: EMU_LAZY(LzLds4k); break;
+        case 4: EMU_LAZY(LzLdsJ); break;
+        case 5: EMU_LAZY(LzLdsJ16k); break;
+        case 6: EMU_LAZY(LzLdsJ8k); break;
+        default: EMU_LAZY(LzLdsJ4k); break;
+        }
 #undef EMU_LAZY
     } else {
         if (g_fast_global) { /* the product's choice: the window read from the input, no LDS ring */
@@ -406,39 +387,122 @@ extern "C" int emu_sort(const uint8_t *src, uint32_t n, uint32_t *sorted_out, ui
     return (int)c.ntiles;
 }
 
+/* One buffer of a plan, kernel by kernel, as zsc_hip_deflate_plan_run enqueues them: open() is the plan's
+ * creation and the kernels before the parser (chains, table, the parser's job, the ZdBuf from the runtime's own
+ * layout with a count of 1), run_parse() the parser, emit() the kernels behind it (checksum, k_huff_plan, k_layout,
+ * k_emit).  Everything a harness builds on top stays here for it to read. */
+struct EmuBuf {
+    EmuChains c;
+    std::vector<uint32_t> syms, outw;
+    std::vector<ZdBlockRec> recs;
+    std::vector<ZdBlockPlan> plans;
+    ZdParseOut po;
+    ZdBuf buf;
+    ZdResult res;
+    LzJob job;
+
+    /* -2: no such level.  run: a run of sections (sections.h), which is raw and takes no table once it has joints;
+     * link_in_parser: the job as a batch gets it that goes to the segmented parser as a whole */
+    int open(const uint8_t *src, uint32_t n, int level, int wrap, int strategy, uint32_t out_cap,
+             const SecRun *run = nullptr, bool table = true, bool link_in_parser = false)
+    {
+        if (level < 1 || level > 9)
+            return -2;
+        build_chains(c, src, n);
+        if (table && (!run || run->sched.empty()))
+            build_table(c, level, strategy);
+        const uint64_t off = 0;
+        const uint32_t more = run && run->more, n0 = run ? run->n0 : n, sched_off = 0,
+                       sched_n = run ? (uint32_t)run->sched.size() : 0u, seg_ok = run && sec_seg_ok(*run);
+        const PlanRuns pr = {&more, &n0, &sched_off, &sched_n, &seg_ok, run ? run->sched.data() : nullptr, sched_n};
+        DplLayout L;
+        uint32_t bad;
+        if (dpl_layout(1, &n, &off, &off, &out_cap, level, wrap, g_wbits, g_mem_level, strategy, run ? &pr : nullptr,
+                       DplKnobs(), L, &bad) != DPL_OK)
+            return -2;
+        buf = L.bufs[0];
+        syms.assign((size_t)n + 64, 0);
+        recs.assign(buf.max_blocks, ZdBlockRec());
+        plans.assign(buf.max_blocks, ZdBlockPlan());
+        po.nsyms = po.nblocks = 0;
+        memset(&res, 0, sizeof res);
+        job.in = c.in.data();
+        job.n = n;
+        job.sorted = c.sorted.data();
+        job.rank = c.rank.data();
+        job.hib = link_in_parser ? nullptr : c.hib.data();
+        job.cnt = link_in_parser ? nullptr : c.cnt.data();
+        job.dir = link_in_parser ? c.dir.data() : nullptr;
+        g_dir = c.dir.data();
+        job.r2 = c.r2.empty() ? nullptr : c.r2.data();
+        job.stair_min = g_stair_min;
+        job.syms = syms.data();
+        job.blocks = recs.data();
+        job.out = &po;
+        job.cfg = level_cfg(level);
+        job.strategy = (uint32_t)strategy;
+        job.more = buf.more;
+        job.sched = pr.sched;
+        job.nsched = sched_n;
+        job.n0 = n0;
+        job.ntot = n;
+        g_job_seg_ok = !run || seg_ok;
+        return 0;
+    }
+
+    /* the kernels run over block slots: a block past max_blocks has none (and layout_buffer refuses the buffer) */
+    void emit()
+    {
+        CkLds ck;
+        res.adler = buf.wrap == 1 ? ck_adler32(c.in.data(), job.n) : buf.wrap == 2 ? ck_crc32(c.in.data(), job.n, &ck) : 0;
+        for (uint32_t b = 0; b < po.nblocks && b < buf.max_blocks; b++) {
+            HpLds hl;
+            memset(&hl, 0x5A, sizeof hl);
+            huff_plan_block(syms.data() + recs[b].sym_begin, &recs[b], buf.strategy, &plans[b], &hl);
+        }
+        outw.assign(((size_t)buf.out_cap + 64) / 4 + 4, 0xCDCDCDCD);
+        layout_buffer(&buf, &po, recs.data(), plans.data(), &res, (uint8_t *)outw.data());
+        for (uint32_t b = 0; b < po.nblocks && b < buf.max_blocks; b++) {
+            BeLds bl;
+            memset(&bl, 0x77, sizeof bl);
+            emit_block(c.in.data(), syms.data() + recs[b].sym_begin, &recs[b], &plans[b], outw.data(), &bl);
+        }
+    }
+
+    /* the stream to the caller; the buffer's status */
+    int give(uint8_t *out, uint32_t *out_len) const
+    {
+        *out_len = res.out_len;
+        if (res.status == 0)
+            memcpy(out, outw.data(), res.out_len);
+        return res.status;
+    }
+};
+
+/* the whole pipeline for one buffer; -2 where the parser cut more blocks than the buffer has slots */
+static int emu_one_buffer(EmuBuf &e, const uint8_t *src, uint32_t n, int level, int wrap, int strategy,
+                          uint32_t out_cap, const SecRun *run = nullptr)
+{
+    if (e.open(src, n, level, wrap, strategy, out_cap, run) != 0)
+        return -2;
+    run_parse(e.job);
+    if (e.po.nblocks > e.buf.max_blocks)
+        return -2;
+    e.emit();
+    return e.res.status;
+}
+
 extern "C" int emu_parse(const uint8_t *src, uint32_t n, int level, int strategy, uint32_t *syms,
                          uint32_t *nsyms, ZdBlockRec *blocks, uint32_t *nblocks)
 {
-    if (level < 1 || level > 9)
+    EmuBuf e;
+    if (e.open(src, n, level, 0, strategy, 0) != 0)
         return -2;
-    EmuChains c;
-    build_chains(c, src, n);
-    build_table(c, level, strategy);
-    LzJob job;
-    ZdParseOut out = {0, 0};
-    job.in = c.in.data();
-    job.n = n;
-    job.sorted = c.sorted.data();
-    job.rank = c.rank.data();
-    job.hib = c.hib.data();
-    job.cnt = c.cnt.data();
-    job.dir = nullptr;
-    g_dir = c.dir.data();
-    job.r2 = c.r2.empty() ? nullptr : c.r2.data();
-    job.stair_min = g_stair_min;
-    job.syms = syms;
-    job.blocks = blocks;
-    job.out = &out;
-    job.cfg = level_cfg(level);
-    job.strategy = (uint32_t)strategy;
-    job.more = 0;
-    job.sched = nullptr;
-    job.nsched = 0;
-    job.n0 = n;
-    job.ntot = n;
-    run_parse(job);
-    *nsyms = out.nsyms;
-    *nblocks = out.nblocks;
+    e.job.syms = syms; /* (straight into the caller's arrays) */
+    e.job.blocks = blocks;
+    run_parse(e.job);
+    *nsyms = e.po.nsyms;
+    *nblocks = e.po.nblocks;
     return 0;
 }
 
@@ -461,69 +525,12 @@ extern "C" uint32_t emu_crc32(const uint8_t *src, uint32_t n)
 extern "C" int emu_compress(const uint8_t *src, uint32_t n, int level, int wrap, int strategy,
                             uint8_t *out, uint32_t out_cap, uint32_t *out_len)
 {
-    if (level < 1 || level > 9)
+    EmuBuf e;
+    if (e.open(src, n, level, wrap, strategy, out_cap) != 0)
         return -2;
-    EmuChains c;
-    build_chains(c, src, n);
-    build_table(c, level, strategy);
-    std::vector<uint32_t> syms((size_t)n + 64);
-    uint32_t max_blocks = n / ((1u << (g_mem_level + 6)) - 1u) + 2;
-    std::vector<ZdBlockRec> recs(max_blocks);
-    std::vector<ZdBlockPlan> plans(max_blocks);
-    ZdParseOut po = {0, 0};
-    LzJob job;
-    job.in = c.in.data();
-    job.n = n;
-    job.sorted = c.sorted.data();
-    job.rank = c.rank.data();
-    job.hib = c.hib.data();
-    job.cnt = c.cnt.data();
-    job.dir = nullptr;
-    g_dir = c.dir.data();
-    job.r2 = c.r2.empty() ? nullptr : c.r2.data();
-    job.stair_min = g_stair_min;
-    job.syms = syms.data();
-    job.blocks = recs.data();
-    job.out = &po;
-    job.cfg = level_cfg(level);
-    job.strategy = (uint32_t)strategy;
-    job.more = 0;
-    job.sched = nullptr;
-    job.nsched = 0;
-    job.n0 = n;
-    job.ntot = n;
-    run_parse(job);
-
-    ZdBuf buf;
-    memset(&buf, 0, sizeof buf);
-    buf.in_len = n;
-    buf.max_blocks = max_blocks;
-    buf.out_cap = out_cap;
-    buf.level = (uint32_t)level;
-    buf.wrap = (uint32_t)wrap;
-    buf.strategy = (uint32_t)strategy;
-    buf.wbits = (uint32_t)g_wbits;
-    ZdResult res;
-    memset(&res, 0, sizeof res);
-    CkLds ck;
-    res.adler = wrap == 1 ? ck_adler32(c.in.data(), n) : wrap == 2 ? ck_crc32(c.in.data(), n, &ck) : 0;
-
-    for (uint32_t b = 0; b < po.nblocks; b++) {
-        HpLds hl;
-        memset(&hl, 0x5A, sizeof hl);
-        huff_plan_block(syms.data() + recs[b].sym_begin, &recs[b], (uint32_t)strategy, &plans[b], &hl);
-    }
-    std::vector<uint32_t> outw(((size_t)out_cap + 64) / 4 + 4, 0xCDCDCDCD);
-    layout_buffer(&buf, &po, recs.data(), plans.data(), &res, (uint8_t *)outw.data());
-    for (uint32_t b = 0; b < po.nblocks; b++) {
-        BeLds bl;
-        memset(&bl, 0x77, sizeof bl);
-        emit_block(c.in.data(), syms.data() + recs[b].sym_begin, &recs[b], &plans[b], outw.data(), &bl);
-    }
-    *out_len = res.out_len;
-    if (res.status == 0)
-        memcpy(out, outw.data(), res.out_len);
-    return res.status;
+    run_parse(e.job);
+    e.emit();
+    return e.give(out, out_len);
 }
 
 extern "C" int emu_uncompress(const uint8_t *src, uint32_t n, int window_bits, uint8_t *dst, uint32_t cap,
@@ -562,84 +569,24 @@ struct EmuSecRunner {
         for (size_t j = 0; j < jobs.size(); j++) {
             SecRun &r = *jobs[j];
             parses++;
-            EmuChains c;
-            build_chains(c, src + r.start, r.n);
-            std::vector<uint32_t> syms((size_t)r.n + 64);
-            const uint32_t max_blocks = r.n / ((1u << (g_mem_level + 6)) - 1u) + 2 + (uint32_t)r.sched.size();
-            std::vector<ZdBlockRec> recs(max_blocks);
-            std::vector<ZdBlockPlan> plans(max_blocks);
-            ZdParseOut po = {0, 0};
-            LzJob job;
-            job.in = c.in.data();
-            job.n = r.n;
-            job.sorted = c.sorted.data();
-            job.rank = c.rank.data();
-            job.hib = c.hib.data();
-            job.cnt = c.cnt.data();
-            job.dir = nullptr;
-            g_dir = c.dir.data();
-            if (r.sched.empty())
-                build_table(c, level, strategy);
-            job.r2 = c.r2.empty() ? nullptr : c.r2.data();
-            job.stair_min = g_stair_min;
-    job.stair_min = g_stair_min;
-                    job.syms = syms.data();
-            job.blocks = recs.data();
-            job.out = &po;
-            job.cfg = level_cfg(level);
-            job.strategy = (uint32_t)strategy;
-            job.more = r.more ? 1u : 0u;
-            job.sched = r.sched.data();
-            job.nsched = (uint32_t)r.sched.size();
-            job.n0 = r.n0;
-            job.ntot = r.n;
-            g_job_seg_ok = sec_seg_ok(r);
-            run_parse(job);
-            if (po.nblocks > max_blocks) {
+            EmuBuf e;
+            const int rc = emu_one_buffer(e, src + r.start, r.n, level, 0, strategy, r.n + (r.n >> 3) + 1024u, &r);
+            if (rc != 0) {
                 if (getenv("ZSC_EMU_DEBUG"))
-                    fprintf(stderr, "emu: run at %u n %u: %u blocks > %u\n", r.start, r.n, po.nblocks, max_blocks);
-                return -2;
+                    fprintf(stderr, "emu: run at %u n %u: status %d (%u blocks of %u, out_len %u cap %u)\n", r.start, r.n,
+                            rc, e.po.nblocks, e.buf.max_blocks, e.res.out_len, e.buf.out_cap);
+                return rc;
             }
-
-            ZdBuf buf;
-            memset(&buf, 0, sizeof buf);
-            buf.in_len = r.n;
-            buf.max_blocks = max_blocks;
-            buf.out_cap = r.n + (r.n >> 3) + 1024u;
-            buf.level = (uint32_t)level;
-            buf.wrap = 0;
-            buf.strategy = (uint32_t)strategy;
-            buf.wbits = (uint32_t)g_wbits;
-            buf.more = job.more;
-            ZdResult res;
-            memset(&res, 0, sizeof res);
-            for (uint32_t b = 0; b < po.nblocks; b++) {
-                HpLds hl;
-                memset(&hl, 0x5A, sizeof hl);
-                huff_plan_block(syms.data() + recs[b].sym_begin, &recs[b], (uint32_t)strategy, &plans[b], &hl);
-            }
-            std::vector<uint32_t> &outw = outs[round][j];
-            outw.assign(((size_t)buf.out_cap + 64) / 4 + 4, 0xCDCDCDCD);
-            layout_buffer(&buf, &po, recs.data(), plans.data(), &res, (uint8_t *)outw.data());
-            if (res.status != 0) {
-                if (getenv("ZSC_EMU_DEBUG"))
-                    fprintf(stderr, "emu: run at %u n %u: layout status %d (out_len %u cap %u)\n", r.start, r.n, res.status, res.out_len, buf.out_cap);
-                return res.status;
-            }
-            for (uint32_t b = 0; b < po.nblocks; b++) {
-                BeLds bl;
-                memset(&bl, 0x77, sizeof bl);
-                emit_block(c.in.data(), syms.data() + recs[b].sym_begin, &recs[b], &plans[b], outw.data(), &bl);
-            }
+            outs[round][j].swap(e.outw);
             r.blocks.clear();
-            for (uint32_t b = 0; b < po.nblocks; b++) {
+            for (uint32_t b = 0; b < e.po.nblocks; b++) {
                 SecBlock sb;
-                sb.upto = recs[b].in_begin + recs[b].in_len;
-                sb.end_bit = b + 1 < po.nblocks ? plans[b + 1].bit_off : res.bits;
-                sb.wend = recs[b].wend;
-                sb.at = recs[b].at;
-                sb.cut = recs[b].cut;
-                sb.last = recs[b].last;
+                sb.upto = e.recs[b].in_begin + e.recs[b].in_len;
+                sb.end_bit = b + 1 < e.po.nblocks ? e.plans[b + 1].bit_off : e.res.bits;
+                sb.wend = e.recs[b].wend;
+                sb.at = e.recs[b].at;
+                sb.cut = e.recs[b].cut;
+                sb.last = e.recs[b].last;
                 r.blocks.push_back(sb);
             }
             r.round = round;

@@ -22,100 +22,41 @@ extern "C" int emu_dindex_compress(const uint8_t *src, uint32_t n, int level, in
     *out_len = 0;
     *blob_len = 0;
     *nblocks = 0;
-    /* the runtime's offloadable() */
-    int wrap = 1, wb = window_bits;
-    if (wb < 0) {
-        wrap = 0;
-        wb = -wb;
-    } else if (wb > 15) {
-        wrap = 2;
-        wb -= 16;
-    }
-    if (wb == 8 && wrap == 1)
-        wb = 9;
-    if (level < 1 || level > 9 || wb < 9 || wb > 15 || mem_level < 1 || mem_level > 9)
+    int wrap, wb;
+    if (level < 1 || !dpl_fold_params(&level, window_bits, mem_level, strategy, &wrap, &wb))
         return -2;
     emu_set_params(wb, mem_level);
     chunk_bytes = dix_chunk_bytes(chunk_bytes);
 
-    EmuChains c;
-    build_chains(c, src, n);
-    build_table(c, level, strategy);
-    std::vector<uint32_t> syms((size_t)n + 64);
-    const uint32_t max_blocks = n / ((1u << (g_mem_level + 6)) - 1u) + 2;
-    std::vector<ZdBlockRec> recs(max_blocks);
-    std::vector<ZdBlockPlan> plans(max_blocks);
-    ZdParseOut po = {0, 0};
-    LzJob job;
-    job.in = c.in.data();
-    job.n = n;
-    job.sorted = c.sorted.data();
-    job.rank = c.rank.data();
-    job.hib = c.hib.data();
-    job.cnt = c.cnt.data();
-    job.dir = nullptr;
-    g_dir = c.dir.data();
-    job.r2 = c.r2.empty() ? nullptr : c.r2.data();
-    job.stair_min = g_stair_min;
-    job.syms = syms.data();
-    job.blocks = recs.data();
-    job.out = &po;
-    job.cfg = level_cfg(level);
-    job.strategy = (uint32_t)strategy;
-    job.more = 0;
-    job.sched = nullptr;
-    job.nsched = 0;
-    job.n0 = n;
-    job.ntot = n;
-    run_parse(job);
-
-    ZdBuf buf;
-    memset(&buf, 0, sizeof buf);
-    buf.in_len = n;
-    buf.max_blocks = max_blocks;
-    buf.out_cap = out_cap;
-    buf.level = (uint32_t)level;
-    buf.wrap = (uint32_t)wrap;
-    buf.strategy = (uint32_t)strategy;
-    buf.wbits = (uint32_t)wb;
-    ZdResult res;
-    memset(&res, 0, sizeof res);
+    EmuBuf e;
+    e.open(src, n, level, wrap, strategy, out_cap);
+    run_parse(e.job);
+    e.emit();
+    e.give(out, out_len);
+    const ZdParseOut &po = e.po;
+    const ZdBuf &buf = e.buf;
+    const ZdResult &res = e.res;
+    const uint32_t max_blocks = buf.max_blocks;
     CkLds ck;
-    res.adler = wrap == 1 ? ck_adler32(c.in.data(), n) : wrap == 2 ? ck_crc32(c.in.data(), n, &ck) : 0;
-    for (uint32_t b = 0; b < po.nblocks && b < max_blocks; b++) {
-        HpLds hl;
-        memset(&hl, 0x5A, sizeof hl);
-        huff_plan_block(syms.data() + recs[b].sym_begin, &recs[b], (uint32_t)strategy, &plans[b], &hl);
-    }
-    std::vector<uint32_t> outw(((size_t)out_cap + 64) / 4 + 4, 0xCDCDCDCD);
-    layout_buffer(&buf, &po, recs.data(), plans.data(), &res, (uint8_t *)outw.data());
-    for (uint32_t b = 0; b < po.nblocks && b < max_blocks; b++) {
-        BeLds bl;
-        memset(&bl, 0x77, sizeof bl);
-        emit_block(c.in.data(), syms.data() + recs[b].sym_begin, &recs[b], &plans[b], outw.data(), &bl);
-    }
-    *out_len = res.out_len;
-    if (res.status == 0)
-        memcpy(out, outw.data(), res.out_len);
 
     /* the index of the sub-batch: k_index_reach, k_index_points, k_index_check */
     const uint32_t nb = po.nblocks <= max_blocks ? po.nblocks : 0u;
     std::vector<uint32_t> reach(max_blocks, 0xDDDDDDDDu);
     for (uint32_t b = 0; b < nb; b++)
-        reach[b] = dix_block_reach(syms.data() + recs[b].sym_begin, &recs[b], &plans[b]);
+        reach[b] = dix_block_reach(e.syms.data() + e.recs[b].sym_begin, &e.recs[b], &e.plans[b]);
     const uint32_t cap = out_cap / chunk_bytes + 1u;
     std::vector<ZidxRec> pts(cap);
     memset(pts.data(), 0xEE, sizeof(ZidxRec) * cap);
     uint32_t npts = 0xEEEEEEEEu;
-    dix_points(&buf, &po, recs.data(), plans.data(), reach.data(), &res, chunk_bytes, pts.data(), cap, &npts);
+    dix_points(&buf, &po, e.recs.data(), e.plans.data(), reach.data(), &res, chunk_bytes, pts.data(), cap, &npts);
     for (uint32_t p = 0; p < npts; p++)
-        pts[p].ck = dix_piece_check(c.in.data(), &pts[p], (uint32_t)wrap, &ck);
+        pts[p].ck = dix_piece_check(e.c.in.data(), &pts[p], (uint32_t)wrap, &ck);
 
     for (uint32_t b = 0; b < nb && b < blocks_cap; b++) {
-        blocks[4 * b + 0] = plans[b].bit_off;
-        blocks[4 * b + 1] = recs[b].in_begin;
-        blocks[4 * b + 2] = recs[b].in_len;
-        blocks[4 * b + 3] = plans[b].type;
+        blocks[4 * b + 0] = e.plans[b].bit_off;
+        blocks[4 * b + 1] = e.recs[b].in_begin;
+        blocks[4 * b + 2] = e.recs[b].in_len;
+        blocks[4 * b + 3] = e.plans[b].type;
     }
     *nblocks = nb;
 

@@ -3,8 +3,8 @@ loaded in chunks of 512, 18 slots) on the lane emulation.
 
 tests/emu_pipe_narrow builds the kernel sources with -DZSC_WAVE_EMU at 64 and at 16 lanes and instantiates
 sg_pipe_step with the narrow type.  Every ring read and every chunk load asserts the window invariant
-(emu_pipe_narrow.cpp), and every run must give the oracle's stage P (symbols and block records).  The sizes lie
-around the places where the narrow ring can go wrong: the window, the ring R, the ring and a chunk C, a window
+(tests/emu_pipe/emu_pipe.cpp, built here with -DPIPE_NARROW), and every run must give the oracle's stage P
+(symbols and block records).  The sizes lie around the places where the narrow ring can go wrong: the window, the ring R, the ring and a chunk C, a window
 and a ring, two and three rings; the kinds force parsers that give up and redo rounds (zero, runs, bitmap) and a
 hand-over at every segment (random).  The cases of tests/parser_cases.py that put a candidate at MAX_DIST and
 around slides and segment hand-overs read the oldest byte the floor allows.

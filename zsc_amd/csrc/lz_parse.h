@@ -60,14 +60,14 @@ struct LzLdsT {
 typedef LzLdsT<ZD_RING, ZD_CHUNK> LzLds;
 /* a buffer that fits the ring whole never slides it, so short buffers can run with a
  * smaller ring and proportionally more waves per CU (the parser is latency-bound) */
-typedef LzLdsT<18432u, 2048u> LzLds16k; /* n <= 18 432: 7 waves per CU */
-typedef LzLdsT<10240u, 2048u> LzLds8k;  /* n <= 10 240: 12 waves per CU */
-typedef LzLdsT<6144u, 2048u> LzLds4k;   /* n <=  6 144: 17 waves per CU */
+typedef LzLdsT<ZD_RING_16K, 2048u> LzLds16k; /* n <= 18 432: 7 waves per CU */
+typedef LzLdsT<ZD_RING_8K, 2048u> LzLds8k;  /* n <= 10 240: 12 waves per CU */
+typedef LzLdsT<ZD_RING_4K, 2048u> LzLds4k;   /* n <=  6 144: 17 waves per CU */
 /* the same with the hole map, for runs of sections that have joints */
 typedef LzLdsT<ZD_RING, ZD_CHUNK, true> LzLdsJ;
-typedef LzLdsT<18432u, 2048u, true> LzLdsJ16k;
-typedef LzLdsT<10240u, 2048u, true> LzLdsJ8k;
-typedef LzLdsT<6144u, 2048u, true> LzLdsJ4k;
+typedef LzLdsT<ZD_RING_16K, 2048u, true> LzLdsJ16k;
+typedef LzLdsT<ZD_RING_8K, 2048u, true> LzLdsJ8k;
+typedef LzLdsT<ZD_RING_4K, 2048u, true> LzLdsJ4k;
 
 /* LDS of the greedy parser (levels 1-3): a 34 KiB ring (2 KiB chunks) leaves room for
  * the one-bit-per-position "was inserted" map deflate_fast needs (it does not index the

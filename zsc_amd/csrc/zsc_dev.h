@@ -36,6 +36,10 @@
 
 #define ZD_RING 36864u         /* LDS window ring of the parser: 32 KiB history + one 4 KiB chunk */
 #define ZD_CHUNK 4096u
+/* the smaller rings of lz_parse.h: a buffer no longer than one of them takes it (deflate_plan_layout.h) */
+#define ZD_RING_16K 18432u
+#define ZD_RING_8K 10240u
+#define ZD_RING_4K 6144u
 
 #define ZD_HDR_BYTES 320u      /* room for one dynamic block header (HLIT..code lengths) */
 

@@ -46,6 +46,7 @@
 #include "lz_parse_simple.h"
 #include "sections.h"
 #include "zsc_dev.h"
+#include "deflate_plan_layout.h"
 
 #include "zsc/zsc_conf_private.h"
 #include "zsc_hip.h"
@@ -1485,11 +1486,6 @@ __global__ __launch_bounds__(64) void k_rsy_finish(const uint8_t *__restrict__ s
 
 namespace {
 
-const ZdLevel kLevels[10] = {
-    {0, 0, 0, 0, 0},         {4, 4, 8, 4, 0},       {4, 5, 16, 8, 0},     {4, 6, 32, 32, 0},
-    {4, 4, 16, 16, 1},       {8, 16, 32, 32, 1},    {8, 16, 128, 128, 1}, {8, 32, 128, 256, 1},
-    {32, 128, 258, 1024, 1}, {32, 258, 258, 4096, 1}};
-
 std::once_flag g_init_once;
 int g_init_status = Z_STREAM_ERROR;
 int g_device = -1; /* the device this process's plans, scratch and kernels live on */
@@ -1661,9 +1657,6 @@ struct DevBuf {
     }
 };
 
-/* the longest buffer one plan entry may be: deflateBound of it stays below 2^29 bytes = 2^32 bits */
-#define ZSC_HIP_MAX_BUFFER 0x1ff00000u
-
 /* The streams rule (zsc_hip.h, "Streams"): a plan has one set of scratch, so what it enqueues is ordered on the
  * device whatever streams it is given, and the host waits only in _results, the accessors and _destroy.  One of
  * these per kind of work -- a plan's runs, its verifications, its packs: the stream the last enqueue of the kind
@@ -1731,17 +1724,9 @@ void work_release(Enqueued &w)
     w = Enqueued();
 }
 
-/* a group of buffers that shares one set of scratch arrays */
-struct SubBatch {
-    uint32_t first = 0, count = 0; /* buffers [first, first+count) of the plan */
-    uint32_t ntiles = 0, nslots = 0;
-    uint64_t nsym_slots = 0;
+/* a group of buffers that shares one set of scratch arrays (deflate_plan_layout.h), and its descriptors on the device */
+struct SubBatch : DplSubShape {
     DevBuf d_bufs, d_tile_owner, d_blk_owner, d_order;
-    /* the length-sorted order (longest first) splits into ring-size classes:
-     * [0,c36) full ring, [c36,c16) <= 18 432 B, [c16,c8) <= 10 240 B, [c8,count) <= 6 144 B */
-    uint32_t c36 = 0, c16 = 0, c8 = 0;
-    uint32_t cseg = 0;  /* [0,cseg) of the length-sorted order go to the segmented parser */
-    bool seg_narrow = false; /* ... in the pipeline's own LDS geometry (k_parse_seg_narrow); fixed when the plan is made */
 };
 
 /* Packing (pack.h): what a plan of either kind holds for it, and the launches */
@@ -2054,12 +2039,6 @@ struct zsc_hip_deflate_plan {
     BgzfState bgzf;
 };
 
-/* The LDS geometry the pipeline runs in when nothing is said (ZSC_HIP_SEG_RING).  The narrow ring pays through
- * the fourth workgroup on a CU and costs through the shorter pipeline (+4.2 % on the
- * headline; 2 to 21 % slower, by class, where a CU is offered three workgroups or fewer), so a sub-batch takes it
- * when it has more long buffers than three per CU, each sub-batch for itself. */
-#define ZSC_SEG_WIDE_WG_PER_CU 3u
-
 /* is the plan one k_parse_seg_narrow is built for?  Plain buffers in the pipeline schedule that would otherwise
  * take k_parse_seg<false, false, 6 or 0> */
 static bool zsc_plan_narrow_able(const zsc_hip_deflate_plan *pl)
@@ -2118,28 +2097,6 @@ extern "C" const char *zsc_hip_device_info(void)
 /* reference deflateBoundNoStream + zsc_compress_get_max_output_size2; defined in zsc_api.c */
 extern "C" ZlibReturn zsc_compress_get_max_output_size2(U32, U32, I32, I32, I32, U32 *);
 
-static bool offloadable(I32 level, I32 window_bits, I32 mem_level, ZlibStrategy strategy, int *wrap,
-                        int *wbits)
-{
-    int wb = window_bits;
-    *wrap = 1;
-    if (wb < 0) {
-        *wrap = 0;
-        wb = -wb;
-    } else if (wb > 15) {
-        *wrap = 2;
-        wb -= 16;
-    }
-    if (wb == 8 && *wrap == 1)
-        wb = 9; /* reference src/deflate.c:329-331 */
-    *wbits = wb;
-    if (level == Z_DEFAULT_COMPRESSION)
-        level = 6;
-    return wb >= 9 && wb <= 15 && mem_level >= 1 && mem_level <= 9 && level >= 1 && level <= 9 &&
-           (strategy == Z_DEFAULT_STRATEGY || strategy == Z_FILTERED || strategy == Z_FIXED ||
-            strategy == Z_HUFFMAN_ONLY || strategy == Z_RLE);
-}
-
 extern "C" ZlibReturn zsc_hip_deflate_plan_layout(U32 count, const U32 *source_lens, I32 level,
                                                   I32 window_bits, I32 mem_level,
                                                   uint64_t *in_offsets, uint64_t *out_offsets,
@@ -2170,19 +2127,6 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_layout(U32 count, const U32 *source_l
         *out_bytes = oo + 64;
     return Z_OK;
 }
-
-namespace {
-/* what a plan of runs of sections (sections.h) knows beyond the lengths */
-struct PlanRuns {
-    const uint32_t *more;      /* per buffer: ZdBuf.more */
-    const uint32_t *n0;        /* per buffer: length of the first section */
-    const uint32_t *sched_off; /* per buffer: first joint in sched[] */
-    const uint32_t *sched_n;
-    const uint32_t *seg_ok;    /* per buffer: sections.h sec_seg_ok */
-    const ZdSched *sched;
-    uint32_t nsched;
-};
-} // namespace
 
 static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const U32 *source_lens,
                               const uint64_t *in_offsets, const uint64_t *out_offsets,
@@ -2255,14 +2199,50 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
     if (zsc_hip_init(-1) != Z_OK)
         return Z_STREAM_ERROR;
     int wrap = 1, wbits = 15;
-    if (!offloadable(level, window_bits, mem_level, strategy, &wrap, &wbits)) {
+    if (!dpl_fold_params(&level, window_bits, mem_level, (int)strategy, &wrap, &wbits)) {
         ZSC_WARN4("zsc_hip: level %d / window_bits %d / mem_level %d / strategy %d is not "
                   "offloaded to the GPU yet (DESIGN.md, out of scope).",
                   level, window_bits, mem_level, (int)strategy);
         return Z_STREAM_ERROR;
     }
-    if (level == Z_DEFAULT_COMPRESSION)
-        level = 6;
+
+    DplKnobs knobs;
+    /* input bytes per sub-batch; the scratch is ~14 B per input byte OF ONE SUB-BATCH.  Measured on
+     * the x4096 batch (11.5 GB): 8 GiB sub-batches 3 641 MB/s with 165 GB of scratch, 4 GiB 3 631 MB/s
+     * with 83 GB, 2 GiB 3 552 MB/s with 41 GB (the tail of every sub-batch's parse is idle time) */
+    knobs.sub_limit = 4096ull << 20;
+    if (const char *e = getenv("ZSC_HIP_SUBBATCH_MB"))
+        knobs.sub_limit = (uint64_t)atoll(e) << 20;
+    if (knobs.sub_limit < (1ull << 20))
+        knobs.sub_limit = 1ull << 20;
+    if (runs)
+        knobs.sub_limit = ~0ull; /* the caller reads the block records back: one set of scratch arrays */
+    knobs.use_seg = getenv("ZSC_HIP_NO_SEG") == nullptr;
+    /* buffers longer than this go to the segmented parser.  Measured on the x4096 batch: 18 432
+     * (round 1: what fits the small rings stays with the wave-per-buffer parser) 2 843 + 37 ms of
+     * parsing, 8 192: 2 853 + 13 ms, 3 072: 2 853 + 0 ms -- a workgroup per 4 KiB file still
+     * beats a wave per file */
+    static const uint32_t seg_min = getenv("ZSC_HIP_SEG_MIN") ? (uint32_t)atoi(getenv("ZSC_HIP_SEG_MIN")) : 3072u;
+    knobs.seg_min = seg_min;
+    knobs.full_ring_only = getenv("ZSC_HIP_FULL_RING") != nullptr;
+    if (const char *e = getenv("ZSC_HIP_SEG_RING"))
+        knobs.ring_said = strcmp(e, "narrow") == 0 ? 2 : strcmp(e, "wide") == 0 ? 1 : 0;
+    knobs.cus = (uint32_t)g_cus;
+
+    DplLayout L;
+    uint32_t bad = 0;
+    const int lrc = dpl_layout(count, source_lens, in_offsets, out_offsets, out_caps, level, wrap, wbits, mem_level,
+                               (int)strategy, runs, knobs, L, &bad);
+    if (lrc == DPL_MEM_ERROR) {
+        ZSC_WARN2("zsc_hip: buffer %u has %u bytes; one buffer (or one run of sections) is limited "
+                  "to 535 822 335 bytes.", bad, source_lens[bad]);
+        return Z_MEM_ERROR;
+    }
+    if (lrc != DPL_OK) {
+        ZSC_WARN1("zsc_hip: buffer %u is not 16-byte aligned in the batch.", bad);
+        return Z_STREAM_ERROR;
+    }
+
     auto *pl = new zsc_hip_deflate_plan();
     pl->count = count;
     pl->level = level;
@@ -2271,158 +2251,37 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
     pl->mem_level = mem_level;
     pl->strategy = (uint32_t)strategy;
     pl->sectioned = runs != nullptr;
-    pl->bufs.resize(count);
-
-    /* input bytes per sub-batch; the scratch is ~14 B per input byte OF ONE SUB-BATCH.  Measured on
-     * the x4096 batch (11.5 GB): 8 GiB sub-batches 3 641 MB/s with 165 GB of scratch, 4 GiB 3 631 MB/s
-     * with 83 GB, 2 GiB 3 552 MB/s with 41 GB (the tail of every sub-batch's parse is idle time) */
-    uint64_t sub_limit = 4096ull << 20;
-    if (const char *e = getenv("ZSC_HIP_SUBBATCH_MB"))
-        sub_limit = (uint64_t)atoll(e) << 20;
-    if (sub_limit < (1ull << 20))
-        sub_limit = 1ull << 20;
-    if (runs)
-        sub_limit = ~0ull; /* the caller reads the block records back: one set of scratch arrays */
-
-    /* cut into sub-batches and number tiles / block slots / symbol slots inside each */
-    uint64_t max_tiles = 0, max_slots = 0, max_syms = 0, max_rank_span = 0, max_count = 0;
-    uint32_t i = 0;
-    while (i < count) {
-        SubBatch sb;
-        sb.first = i;
-        uint64_t bytes = 0;
-        while (i < count && (sb.count == 0 || bytes + source_lens[i] <= sub_limit)) {
-            const uint32_t n = source_lens[i];
-            if (n >= ZSC_HIP_MAX_BUFFER) {
-                /* bit positions inside one stream are 32-bit (ZdBlockPlan.bit_off, the layout and
-                 * emit kernels): a stream must stay below 2^32 bits */
-                ZSC_WARN2("zsc_hip: buffer %u has %u bytes; one buffer (or one run of sections) is limited "
-                          "to 535 822 335 bytes.", i, n);
-                delete pl;
-                return Z_MEM_ERROR;
-            }
-            if (in_offsets[i] & 15u || out_offsets[i] & 15u) {
-                ZSC_WARN1("zsc_hip: buffer %u is not 16-byte aligned in the batch.", i);
-                delete pl;
-                return Z_STREAM_ERROR;
-            }
-            ZdBuf &b = pl->bufs[i];
-            memset(&b, 0, sizeof b);
-            b.in_off = in_offsets[i];
-            b.out_off = out_offsets[i];
-            b.in_len = n;
-            b.out_cap = out_caps[i];
-            b.ntiles = n == 0 ? 1u : (uint32_t)(((uint64_t)n + ZD_TILE - 1) / ZD_TILE);
-            b.tile0 = sb.ntiles;
-            b.max_blocks = n / ((1u << (mem_level + 6)) - 1u) + 2;
-            if (runs) {
-                b.more = runs->more[i];
-                b.n0 = runs->n0[i];
-                b.sched_off = runs->sched_off[i];
-                b.sched_n = runs->sched_n[i];
-                b.seg_ok = runs->seg_ok[i];
-                b.max_blocks += b.sched_n; /* a joint can cut a block */
-            } else {
-                b.n0 = n;
-            }
-            b.blk0 = sb.nslots;
-            b.sym_off = sb.nsym_slots;
-            b.rank_off = sb.nsym_slots; /* one u16 per (padded) input position */
-            b.level = (uint32_t)level;
-            b.wrap = (uint32_t)wrap;
-            b.strategy = (uint32_t)strategy;
-            b.wbits = (uint32_t)wbits;
-            sb.ntiles += b.ntiles;
-            sb.nslots += b.max_blocks;
-            sb.nsym_slots += ((uint64_t)n + 64u) & ~63ull;
-            bytes += n;
-            sb.count++;
-            i++;
-        }
-        max_tiles = std::max<uint64_t>(max_tiles, sb.ntiles);
-        max_slots = std::max<uint64_t>(max_slots, sb.nslots);
-        max_syms = std::max<uint64_t>(max_syms, sb.nsym_slots);
-        max_rank_span = std::max<uint64_t>(max_rank_span, sb.nsym_slots + 64);
-        max_count = std::max<uint64_t>(max_count, sb.count);
-        pl->subs.push_back(std::move(sb));
-    }
-
-    pl->use_seg = getenv("ZSC_HIP_NO_SEG") == nullptr && kLevels[level].slow;
+    pl->bufs = std::move(L.bufs);
+    pl->use_seg = L.use_seg;
+    pl->table_min = knobs.seg_min;
+    pl->seg_ring_said = knobs.ring_said;
     if (const char *e = getenv("ZSC_HIP_SEG_PIPE"))
         pl->seg_pipe = atoi(e) != 0;
-    if (const char *e = getenv("ZSC_HIP_SEG_RING"))
-        pl->seg_ring_said = strcmp(e, "narrow") == 0 ? 2 : strcmp(e, "wide") == 0 ? 1 : 0;
     pl->link_kernel = getenv("ZSC_HIP_LINK_KERNEL") != nullptr;
     pl->fast_ring = getenv("ZSC_HIP_FAST_RING") != nullptr;
     /* per-sub-batch descriptor arrays */
-    for (SubBatch &sb : pl->subs) {
-        std::vector<uint32_t> tile_owner(sb.ntiles), blk_owner(sb.nslots), order(sb.count);
-        for (uint32_t k = 0; k < sb.count; k++) {
-            const ZdBuf &b = pl->bufs[sb.first + k];
-            for (uint32_t t = 0; t < b.ntiles; t++)
-                tile_owner[b.tile0 + t] = k;
-            for (uint32_t s = 0; s < b.max_blocks; s++)
-                blk_owner[b.blk0 + s] = k;
-            order[k] = k;
+    pl->subs.resize(L.subs.size());
+    for (size_t j = 0; j < L.subs.size(); j++) {
+        const DplSub &ls = L.subs[j];
+        SubBatch &sb = pl->subs[j];
+        static_cast<DplSubShape &>(sb) = ls;
+        const struct {
+            DevBuf *d;
+            const void *src;
+            uint64_t bytes;
+        } up[4] = {{&sb.d_bufs, &pl->bufs[sb.first], sizeof(ZdBuf) * sb.count},
+                   {&sb.d_tile_owner, ls.tile_owner.data(), 4ull * sb.ntiles},
+                   {&sb.d_blk_owner, ls.blk_owner.data(), 4ull * sb.nslots},
+                   {&sb.d_order, ls.order.data(), 4ull * sb.count}};
+        for (const auto &u : up) {
+            if (!u.d->ensure(u.bytes)) {
+                zsc_hip_deflate_plan_destroy(pl);
+                return Z_MEM_ERROR;
+            }
+            HIP_TRY(hipMemcpy(u.d->p, u.src, u.bytes, hipMemcpyHostToDevice),
+                    { zsc_hip_deflate_plan_destroy(pl); return Z_MEM_ERROR; });
+            pl->scratch_bytes += u.d->bytes;
         }
-        /* buffers longer than this go to the segmented parser.  Measured on the x4096 batch: 18 432
-         * (round 1: what fits the small rings stays with the wave-per-buffer parser) 2 843 + 37 ms of
-         * parsing, 8 192: 2 853 + 13 ms, 3 072: 2 853 + 0 ms -- a workgroup per 4 KiB file still
-         * beats a wave per file */
-        static const uint32_t seg_min = getenv("ZSC_HIP_SEG_MIN") ? (uint32_t)atoi(getenv("ZSC_HIP_SEG_MIN")) : 3072u;
-        pl->table_min = seg_min;
-        /* longest first; those the segmented parser may take come first */
-        auto seg_able = [&](uint32_t k) {
-            const ZdBuf &b = pl->bufs[sb.first + k];
-            return pl->use_seg && b.in_len > seg_min && (b.sched_n == 0 || b.seg_ok);
-        };
-        auto klass = [&](uint32_t k) { return seg_able(k) ? 1 : 2; };
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t c) {
-            const int ka = klass(a), kc = klass(c);
-            if (ka != kc)
-                return ka < kc;
-            return pl->bufs[sb.first + a].in_len > pl->bufs[sb.first + c].in_len;
-        });
-        {
-            const bool full_only = getenv("ZSC_HIP_FULL_RING") != nullptr;
-            uint32_t k = 0;
-            auto len_at = [&](uint32_t idx) { return pl->bufs[sb.first + order[idx]].in_len; };
-            while (k < sb.count && seg_able(order[k]))
-                k++;
-            sb.cseg = k;
-            sb.seg_narrow = pl->seg_ring_said == 2 ||
-                            (pl->seg_ring_said == 0 && sb.cseg > ZSC_SEG_WIDE_WG_PER_CU * (uint32_t)g_cus);
-            while (k < sb.count && (full_only || len_at(k) > 18432u))
-                k++;
-            sb.c36 = k;
-            while (k < sb.count && len_at(k) > 10240u)
-                k++;
-            sb.c16 = k;
-            while (k < sb.count && len_at(k) > 6144u)
-                k++;
-            sb.c8 = k;
-        }
-        bool ok = sb.d_bufs.ensure(sizeof(ZdBuf) * sb.count) &&
-                  sb.d_tile_owner.ensure(4ull * std::max(1u, sb.ntiles)) &&
-                  sb.d_blk_owner.ensure(4ull * std::max(1u, sb.nslots)) &&
-                  sb.d_order.ensure(4ull * sb.count);
-        if (!ok) {
-            zsc_hip_deflate_plan_destroy(pl);
-            return Z_MEM_ERROR;
-        }
-        HIP_TRY(hipMemcpy(sb.d_bufs.p, &pl->bufs[sb.first], sizeof(ZdBuf) * sb.count,
-                          hipMemcpyHostToDevice),
-                { zsc_hip_deflate_plan_destroy(pl); return Z_MEM_ERROR; });
-        HIP_TRY(hipMemcpy(sb.d_tile_owner.p, tile_owner.data(), 4ull * sb.ntiles,
-                          hipMemcpyHostToDevice),
-                { zsc_hip_deflate_plan_destroy(pl); return Z_MEM_ERROR; });
-        HIP_TRY(hipMemcpy(sb.d_blk_owner.p, blk_owner.data(), 4ull * sb.nslots,
-                          hipMemcpyHostToDevice),
-                { zsc_hip_deflate_plan_destroy(pl); return Z_MEM_ERROR; });
-        HIP_TRY(hipMemcpy(sb.d_order.p, order.data(), 4ull * sb.count, hipMemcpyHostToDevice),
-                { zsc_hip_deflate_plan_destroy(pl); return Z_MEM_ERROR; });
-        pl->scratch_bytes += sb.d_bufs.bytes + sb.d_tile_owner.bytes + sb.d_blk_owner.bytes +
-                             sb.d_order.bytes;
     }
 
     if (runs && runs->nsched) {
@@ -2434,11 +2293,8 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
         }
         pl->scratch_bytes += pl->d_sched.bytes;
     }
-    uint64_t max_seg = 0;
-    for (const SubBatch &sb : pl->subs)
-        max_seg = std::max<uint64_t>(max_seg, sb.cseg);
-    if (pl->use_seg && max_seg) {
-        if (!pl->d_seg_tok.ensure(max_seg * SG_SCRATCH_WORDS * 4ull)) {
+    if (pl->use_seg && L.max_seg) {
+        if (!pl->d_seg_tok.ensure(L.max_seg * SG_SCRATCH_WORDS * 4ull)) {
             zsc_hip_deflate_plan_destroy(pl);
             return Z_MEM_ERROR;
         }
@@ -2448,28 +2304,28 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
     /* shared scratch: sorted (4 B/position), tmp aliased with the symbol stream
      * (4 B/position, tmp is dead once the sort kernel ends), rank (2 B/position,
      * indexed by input offset), dir (2 B/position), block records + plans */
-    const uint64_t tile_words = max_tiles * ZD_TILE;
+    const uint64_t tile_words = L.max_tiles * ZD_TILE;
     bool ok = pl->d_sorted.ensure(tile_words * 4) &&
-              pl->d_tmp_syms.ensure(std::max<uint64_t>(tile_words, max_syms) * 4) &&
-              pl->d_rank.ensure(max_rank_span * 2) && pl->d_hib.ensure(max_rank_span * 2) &&
-              pl->d_cnt.ensure(max_rank_span * 4) &&
-              pl->d_dir.ensure(max_tiles * ZD_DIR_STRIDE * 2) &&
-              pl->d_recs.ensure(max_slots * sizeof(ZdBlockRec)) &&
-              pl->d_plans.ensure(max_slots * sizeof(ZdBlockPlan)) &&
-              pl->d_pout.ensure(max_count * sizeof(ZdParseOut)) &&
+              pl->d_tmp_syms.ensure(std::max<uint64_t>(tile_words, L.max_syms) * 4) &&
+              pl->d_rank.ensure(L.max_rank_span * 2) && pl->d_hib.ensure(L.max_rank_span * 2) &&
+              pl->d_cnt.ensure(L.max_rank_span * 4) &&
+              pl->d_dir.ensure(L.max_tiles * ZD_DIR_STRIDE * 2) &&
+              pl->d_recs.ensure(L.max_slots * sizeof(ZdBlockRec)) &&
+              pl->d_plans.ensure(L.max_slots * sizeof(ZdBlockPlan)) &&
+              pl->d_pout.ensure(L.max_count * sizeof(ZdParseOut)) &&
               pl->d_res.ensure((uint64_t)std::max(1u, count) * sizeof(ZdResult));
     /* the match table: levels 4-9 with the default window and hash size, for the buffers the
      * segmented parser takes; the match-finding strategies (default, filtered, fixed) share it */
     /* Off unless asked for (ZSC_HIP_TABLE=1): measured on the MI355X the table
      * kernel costs what the hops it buys save -- 23 ms per 403 MB of text for 40 % of the loop tops. */
-    pl->use_table = getenv("ZSC_HIP_TABLE") != nullptr && pl->use_seg && max_seg != 0 && wbits == 15 &&
+    pl->use_table = getenv("ZSC_HIP_TABLE") != nullptr && pl->use_seg && L.max_seg != 0 && wbits == 15 &&
                     mem_level == 8 && strategy != Z_HUFFMAN_ONLY && strategy != Z_RLE;
     if (const char *e = getenv("ZSC_HIP_STAIR_MIN")) /* (debugging / tuning aid) */
         pl->stair_min = (uint32_t)atoi(e);
     if (const char *e = getenv("ZSC_HIP_TABLE_CAP")) /* (debugging / tuning aid) */
         pl->table_cap = (uint32_t)atoi(e);
     if (ok && pl->use_table)
-        ok = pl->d_r2.ensure(max_rank_span * 4);
+        ok = pl->d_r2.ensure(L.max_rank_span * 4);
     if (!ok) {
         zsc_hip_deflate_plan_destroy(pl);
         return Z_MEM_ERROR;
@@ -2538,11 +2394,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
     pl->last_stream = st;
     const uint8_t *in = (const uint8_t *)d_input;
     uint8_t *out = (uint8_t *)d_output;
-    ZdLevel cfg = kLevels[pl->level];
-    cfg.wsize = 1u << pl->wbits;                 /* reference src/deflate.c:343-346 */
-    cfg.max_dist = cfg.wsize - ZD_MIN_LOOKAHEAD; /* MAX_DIST, include/zsc/deflate.h:304 */
-    cfg.sym_cap = (1u << (pl->mem_level + 6)) - 1u; /* lit_bufsize - 1, :362 + deflate.h:338-354 */
-    cfg.hbits = (uint32_t)pl->mem_level + 7u;
+    const ZdLevel cfg = dpl_level(pl->level, pl->wbits, pl->mem_level);
 
     const size_t nev = pl->events_used + pl->subs.size() * ZSC_HIP_NKERNELS;
     if (pl->profile) {
@@ -3510,8 +3362,8 @@ extern "C" ZlibReturn zsc_hip_store_batch(U32 count, const U8 *const *sources, c
         return Z_OK;
     if (zsc_hip_init(-1) != Z_OK)
         return Z_STREAM_ERROR;
-    int wrap = 1, wbits = 15;
-    if (!offloadable(1, window_bits, mem_level, Z_DEFAULT_STRATEGY, &wrap, &wbits))
+    int wrap = 1, wbits = 15, level = 1;
+    if (!dpl_fold_params(&level, window_bits, mem_level, Z_DEFAULT_STRATEGY, &wrap, &wbits))
         return Z_STREAM_ERROR;
     /* zlib header of level 0: level_flags 0 (src/deflate.c:1031-1049); gzip XFL 4 (:1075-1078) */
     uint32_t zh = (8u + (((uint32_t)wbits - 8u) << 4)) << 8;
@@ -3851,14 +3703,12 @@ static ZlibReturn sections_on_device(U32 count, const uint8_t *d_src, const uint
     if (zsc_hip_init(-1) != Z_OK)
         return Z_STREAM_ERROR;
     int wrap = 1, wbits = 15;
-    if (!offloadable(level, window_bits, mem_level, strategy, &wrap, &wbits)) {
+    if (!dpl_fold_params(&level, window_bits, mem_level, (int)strategy, &wrap, &wbits)) {
         ZSC_WARN4("zsc_hip: level %d / window_bits %d / mem_level %d / strategy %d is not "
                   "offloaded to the GPU yet (DESIGN.md, out of scope).",
                   level, window_bits, mem_level, (int)strategy);
         return Z_STREAM_ERROR;
     }
-    if (level == Z_DEFAULT_COMPRESSION)
-        level = 6;
 
     /* wrapper header as deflate() writes it (src/deflate.c:1031-1049, :1068-1082) */
     uint32_t zh = (8u + (((uint32_t)wbits - 8u) << 4)) << 8;
