@@ -123,9 +123,9 @@ ZlibReturn zsc_hip_uncompress_batch(U32 count, const U8 *const *sources, U32 *so
  *     for the plan's last run: a run that another _run follows before _results is left where its first pass
  *     got to.
  *   - a plan has ONE set of scratch.  A _run enqueued on another stream than the plan's unfinished earlier
- *     work -- a run, a verification, a pack or a _bgzf -- waits for that work on the device (an event behind each
- *     enqueue, hipStreamWaitEvent only where the streams differ); the host does not wait.  A plan that only
- *     ever sees one stream enqueues nothing for this but one event record per call.
+ *     work -- a run, a verification, a pack, a _bgzf or a _zip -- waits for that work on the device (an event
+ *     behind each enqueue, hipStreamWaitEvent only where the streams differ); the host does not wait.  A plan
+ *     that only ever sees one stream enqueues nothing for this but one event record per call.
  *   - _results, every accessor and _destroy wait, on the host, for all of the plan's work, whatever streams
  *     it went to: every stream the plan was given since the last such wait is synchronised, so it must still
  *     exist then.
@@ -828,6 +828,85 @@ ZlibReturn zsc_hip_deflate_plan_bgzf_results(zsc_hip_deflate_plan *plan, uint64_
 ZlibReturn zsc_hip_bgzf_compress_batch(U32 nfiles, const U8 *const *sources, const uint64_t *source_lens,
                                        U8 *const *dests, uint64_t *dest_lens, I32 *statuses, I32 level,
                                        I32 mem_level, ZlibStrategy strategy, U32 block_bytes);
+
+/* ZIP archives -------------------------------------------------------------------
+ *
+ * A gzip deflate plan's streams written out as ZIP archives -- the container of .npz, wheels, jars and OOXML / ODF
+ * documents -- on the device (zsc_amd/csrc/zip.h).  An archive is a run of consecutive
+ * buffers of the plan, arch_first[a] .. arch_first[a + 1] (a run may be empty).  Its image, all little-endian,
+ * with n the buffer's name length and S the plan's stream for the buffer (out_len bytes):
+ *
+ *   entry, one per buffer in buffer order:
+ *     local header (30): 50 4b 03 04 | version needed 20 | flags | method 8 | DOS time | DOS date | CRC-32 |
+ *                        compressed size = out_len - 18 | uncompressed size | n | extra length 0
+ *     the name (n bytes), then S[10 : out_len - 8], unchanged.  CRC-32 and the uncompressed size are S's last 8
+ *     bytes.
+ *   central directory, one record per buffer in the same order:
+ *     record (46):       50 4b 01 02 | made by 20 (system 0) | version needed 20 | flags, method, time, date,
+ *                        CRC-32 and sizes as in the local header | n | extra length 0 | comment length 0 |
+ *                        disk 0 | internal attributes 0 | external attributes 0 | the local header's offset from
+ *                        the archive's start
+ *     the name again.
+ *   end:
+ *     with 65 535 entries or more, first the ZIP64 end record (56): 50 4b 06 06 | size 44 (8 bytes) | made by 45 |
+ *                        needed 45 | disk 0 | directory's disk 0 | the count twice (8 bytes each) | the
+ *                        directory's size | its offset (8 bytes each)
+ *     and its locator (20): 50 4b 06 07 | disk 0 | the ZIP64 end record's offset (8 bytes) | 1 disk
+ *     then always the end record (22): 50 4b 05 06 | disk 0 | directory's disk 0 | the count twice, saturated at
+ *                        0xFFFF | the directory's size | its offset | comment length 0
+ *
+ * flags is 0x0800 with ZSC_HIP_ZIP_UTF8, else 0; there is no data descriptor: every size is known before a header
+ * is written.  dos_datetime[i] is date << 16 | time; NULL means 0x00210000, 1980-01-01 00:00:00.  Names are bytes
+ * the library does not interpret, 0 to 65 535 of them; buffer i's are names[name_offsets[i] .. name_offsets[i+1]).
+ * Archives start at multiples of align (a power of two from 1 to 4096, as with _pack) and the bytes from an
+ * archive's end to the next one's start are zeros.  An archive FAILS alone -- it takes no room in the image and
+ * the others are what they are without it -- with Z_BUF_ERROR where one of its buffers has a status other than
+ * Z_OK, and with Z_MEM_ERROR where it would be longer than 4 294 967 295 bytes (no ZIP64 offsets or sizes: the
+ * caller splits).  Entry sizes always fit 32 bits.  CPython's zipfile reads these archives; a raw plain inflate
+ * plan over data_offsets and the compressed sizes reads the entries back on the device.
+ *
+ * _zip_enable: before _run.  Z_STREAM_ERROR, with the plan left as it was, for a plan whose wrapper is not gzip, a
+ *   plan of sections, an arch_first that does not ascend from 0 to count, a name above 65 535 bytes or
+ *   descending name_offsets, unknown flags, or a bad align.  Calling it again replaces everything.  names,
+ *   name_offsets (count + 1) and dos_datetime (count, or NULL) are host memory, copied.  Allocates the names, 44
+ *   bytes per buffer (48 with dos_datetime), 36 per archive and 8 per 1 024 archives for the scan's partial sums,
+ *   counted in _scratch_bytes.  Independent of _pack_enable, _bgzf_enable, _index_enable and _verify_enable: all
+ *   may be on.  A plan that never calls it allocates and launches exactly what it did without these functions.
+ * _zip: asynchronous on hip_stream; enqueues kernels only -- no allocation, no synchronisation, no copy from or
+ *   to the host.  Valid after a _run on the same stream or after _results, any number of times.  d_output is the
+ *   run's output or a copy of it at the plan's offsets; of each stream the whole 16-byte granules that hold one
+ *   of its bytes are read.  d_image is 16-byte aligned and image_cap bytes long: bytes [0, total) are each
+ *   written exactly once and nothing at or behind total; with total > image_cap nothing is written at all.
+ *   Ordered against the plan's runs like a pack (see "Streams").
+ * _zip_results: waits for the last _zip.  Every pointer may be NULL.  arch_offsets[a]: where archive a starts,
+ *   arch_offsets[narchives] == *total; arch_lens[a]: its length without the zeros behind it, 0 for a failed one;
+ *   arch_statuses[a]: Z_OK, Z_BUF_ERROR or Z_MEM_ERROR; entry_offsets[i] and data_offsets[i]: where buffer i's
+ *   local header and its DEFLATE body start in the image; dir_offsets[a]: where archive a's central directory
+ *   starts -- all three the archive's offset for a failed archive --; ms: the device time of that _zip's
+ *   launches.  Z_BUF_ERROR where total > image_cap, the tables filled all the same; Z_STREAM_ERROR on a plan that
+ *   never enabled this or never called _zip. */
+#define ZSC_HIP_ZIP_UTF8 1u /* names are UTF-8: general purpose bit 11 */
+ZlibReturn zsc_hip_deflate_plan_zip_enable(zsc_hip_deflate_plan *plan, U32 narchives, const U32 *arch_first,
+                                           const U8 *names, const uint64_t *name_offsets, const U32 *dos_datetime,
+                                           U32 flags, U32 align);
+ZlibReturn zsc_hip_deflate_plan_zip(zsc_hip_deflate_plan *plan, const void *d_output, void *d_image,
+                                    uint64_t image_cap, void *hip_stream);
+ZlibReturn zsc_hip_deflate_plan_zip_results(zsc_hip_deflate_plan *plan, uint64_t *arch_offsets, uint64_t *arch_lens,
+                                            I32 *arch_statuses, uint64_t *entry_offsets, uint64_t *data_offsets,
+                                            uint64_t *dir_offsets, uint64_t *total, float *ms);
+
+/* Host memory: narchives archives of named buffers compressed into narchives ZIP files.  Archive a is the buffers
+ * arch_first[a] .. arch_first[a + 1] of count = arch_first[narchives]; buffer i is sources[i], source_lens[i]
+ * bytes, named names[name_offsets[i] .. name_offsets[i + 1]).  One upload, one plan, one run, one _zip and one
+ * copy back per archive.  dest_lens[a]: in, the room at dests[a]; out, the archive's length.  statuses[a] (may be
+ * NULL): Z_OK; Z_BUF_ERROR or Z_MEM_ERROR where the archive failed (the length is then 0); Z_BUF_ERROR where the
+ * room is too small (nothing is copied, the length says what it takes).  An empty archive is the 22 bytes of an
+ * end record.  Returns Z_OK when the batch ran; Z_STREAM_ERROR for what _zip_enable refuses.  Level 0 is
+ * Z_STREAM_ERROR, as in the packed batch. */
+ZlibReturn zsc_hip_zip_compress_batch(U32 narchives, const U32 *arch_first, const U8 *const *sources,
+                                      const U32 *source_lens, const U8 *names, const uint64_t *name_offsets,
+                                      const U32 *dos_datetime, U32 flags, U8 *const *dests, uint64_t *dest_lens,
+                                      I32 *statuses, I32 level, I32 mem_level, ZlibStrategy strategy);
 
 /* BGZF ranges ---------------------------------------------------------------
  *

@@ -35,6 +35,8 @@ Host-side mirror (Python, ctypes) of the C ABI exported by ``libzsc_hip.so``:
 * :class:`BgzfIndex`, :class:`BgzfRangesPlan` (``InflatePlan.bgzf_ranges``), :func:`bgzf_read_ranges` -- ranges read out
   of BGZF files by uncompressed or virtual offset: a member index built from the headers alone (``to_gzi`` /
   ``from_gzi``), and a plan that decodes only the members its requests touch;
+* :func:`zip_compress_batch` -- lists of named buffers written as ZIP archives (``.npz``, wheels, jars, OOXML), which
+  CPython's ``zipfile`` reads (``DeflatePlan.zip_enable`` / ``zip`` / ``zip_results``);
 * :class:`DeflatePlan` -- device-resident batches (inputs and outputs stay in HBM).
 
 There is no CPU codec here: if the HIP library is missing, import fails loudly.
@@ -56,5 +58,6 @@ from .api import (  # noqa: F401
     VERIFY_DISTANCE, VERIFY_MATCH, VERIFY_LENGTH, VERIFY_BIT_END, VERIFY_TRAILER,
     PACK_TILE, unpack, compress_batch_packed, uncompress_batch_packed, PackedCallError,
     bgzf_compress_batch, BgzfIndex, BgzfRangesPlan, bgzf_read_ranges, BGZF_VOFFSETS,
+    zip_compress_batch, ZIP_UTF8,
     GzHeader, gz_header_for_writing, gz_header_for_reading, gz_header_fields,
 )

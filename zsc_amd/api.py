@@ -177,6 +177,14 @@ def _load() -> C.CDLL:
     L.zsc_hip_deflate_plan_bgzf_results.argtypes = [C.c_void_p, u64p, u64p, i32p, u64p, u64p, C.POINTER(C.c_float)]
     L.zsc_hip_bgzf_compress_batch.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u64p, C.POINTER(C.c_void_p), u64p,
                                               i32p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
+    L.zsc_hip_deflate_plan_zip_enable.argtypes = [C.c_void_p, C.c_uint32, u32p, C.c_char_p, u64p, u32p, C.c_uint32,
+                                                  C.c_uint32]
+    L.zsc_hip_deflate_plan_zip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.zsc_hip_deflate_plan_zip_results.argtypes = [C.c_void_p, u64p, u64p, i32p, u64p, u64p, u64p, u64p,
+                                                   C.POINTER(C.c_float)]
+    L.zsc_hip_zip_compress_batch.argtypes = [C.c_uint32, u32p, C.POINTER(C.c_char_p), u32p, C.c_char_p, u64p, u32p,
+                                             C.c_uint32, C.POINTER(C.c_void_p), u64p, i32p, C.c_int32, C.c_int32,
+                                             C.c_int32]
     L.zsc_hip_bgzf_index_build.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, u32p, u64p, C.c_void_p]
     L.zsc_hip_bgzf_index_import_gzi.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                                 C.c_uint64, C.c_void_p]
@@ -768,6 +776,48 @@ def bgzf_compress_batch(files: Sequence[bytes], level: int = 6, block_bytes: int
     if rc != Z_OK:
         raise PackedCallError("zsc_hip_bgzf_compress_batch", rc, [])
     return [b.raw[:dlen[f]] if stat[f] == Z_OK else b"" for f, b in enumerate(bufs)], list(stat)[:n]
+
+
+ZIP_UTF8 = 1
+
+
+def zip_compress_batch(archives: Sequence[Sequence[Tuple[bytes, bytes]]], level: int = 6,
+                       mem_level: int = DEF_MEM_LEVEL, strategy: int = Z_DEFAULT_STRATEGY,
+                       dos_datetime: Sequence[int] | None = None, utf8: bool = False,
+                       dest_caps: Sequence[int] | None = None) -> Tuple[List[bytes], List[int]]:
+    """zsc_hip_zip_compress_batch: archives[a] is a list of (name_bytes, data); every archive comes back as a ZIP
+    file of its own, its entries in that order (method 8, no data descriptors; the ZIP64 end records from 65 535
+    entries on).  dos_datetime: one date << 16 | time per entry over all archives (default 1980-01-01 00:00:00);
+    utf8 sets the entries' UTF-8 flag.  Returns (files, statuses): an archive whose status is not Z_OK is b"" --
+    it would pass 4 294 967 295 bytes (Z_MEM_ERROR), or dest_caps[a] (default: the worst case) was too small
+    (Z_BUF_ERROR).  PackedCallError where the call as a whole fails."""
+    na = len(archives)
+    first, names, datas = [0], [], []
+    for arch in archives:
+        for nm, data in arch:
+            names.append(bytes(nm))
+            datas.append(bytes(data))
+        first.append(len(datas))
+    n = len(datas)
+    if dest_caps is None:  # (zlib's conservative bound on a deflate body)
+        dest_caps = [sum(76 + 2 * len(names[i]) + len(datas[i]) + (len(datas[i]) >> 3) + (len(datas[i]) >> 8) +
+                         (len(datas[i]) >> 9) + 64 for i in range(first[a], first[a + 1])) + 98 for a in range(na)]
+    offs = [0]
+    for nm in names:
+        offs.append(offs[-1] + len(nm))
+    bufs = [C.create_string_buffer(max(c, 1)) for c in dest_caps]
+    srcs = (C.c_char_p * max(n, 1))(*datas)
+    slen = (C.c_uint32 * max(n, 1))(*[len(d) for d in datas])
+    dsts = (C.c_void_p * max(na, 1))(*[C.addressof(b) for b in bufs])
+    dlen = (C.c_uint64 * max(na, 1))(*dest_caps)
+    stat = (C.c_int32 * max(na, 1))()
+    dt = None if dos_datetime is None else (C.c_uint32 * max(n, 1))(*dos_datetime)
+    rc = lib.zsc_hip_zip_compress_batch(na, (C.c_uint32 * (na + 1))(*first), srcs, slen, b"".join(names),
+                                        (C.c_uint64 * (n + 1))(*offs), dt, ZIP_UTF8 if utf8 else 0, dsts, dlen, stat,
+                                        level, mem_level, strategy)
+    if rc != Z_OK:
+        raise PackedCallError("zsc_hip_zip_compress_batch", rc, [])
+    return [b.raw[:dlen[a]] if stat[a] == Z_OK else b"" for a, b in enumerate(bufs)], list(stat)[:na]
 
 
 def uncompress_batch_packed(image: bytes, offsets: Sequence[int], lens: Sequence[int], dest_caps: Sequence[int],
@@ -1468,6 +1518,63 @@ class DeflatePlan(_Packing):
         if getattr(self, "_bgzf_ms", None) is None:
             raise RuntimeError("no bgzf_results() yet")
         return self._bgzf_ms
+
+    def zip_enable(self, arch_first: Sequence[int], names: Sequence[bytes],
+                   dos_datetime: Optional[Sequence[int]] = None, utf8: bool = False, align: int = 1) -> None:
+        """Before run(), on a gzip plan (window_bits 31): the plan can write its streams as ZIP archives, archive a
+        the buffers arch_first[a] .. arch_first[a + 1] (narchives + 1 values ascending from 0 to count), buffer i
+        named names[i] (bytes, 65 535 at the most), each archive at a multiple of align.  dos_datetime[i] is
+        date << 16 | time (default 1980-01-01 00:00:00); utf8 sets the entries' UTF-8 flag.  Calling it again
+        replaces everything.  ValueError, the plan as it was, where the library refuses."""
+        na = len(arch_first) - 1
+        if na < 0 or len(names) != self.count or (dos_datetime is not None and len(dos_datetime) != self.count):
+            raise ValueError("arch_first holds narchives + 1 values; names and dos_datetime one per buffer")
+        offs = [0]
+        for nm in names:
+            offs.append(offs[-1] + len(nm))
+        dt = None if dos_datetime is None else (C.c_uint32 * max(self.count, 1))(*dos_datetime)
+        rc = lib.zsc_hip_deflate_plan_zip_enable(self._h, na, (C.c_uint32 * (na + 1))(*arch_first), b"".join(names),
+                                                 (C.c_uint64 * (self.count + 1))(*offs), dt, ZIP_UTF8 if utf8 else 0,
+                                                 align)
+        if rc != Z_OK:
+            raise ValueError(f"zsc_hip_deflate_plan_zip_enable failed: {rc}")
+        self._zip_archives = na
+
+    def zip(self, d_output: int, d_image: int, cap: int, stream: int = 0) -> int:
+        """After run() on the same stream, or after results(), any number of times: enqueue the writing of the
+        archives from the streams at d_output (the run's output or a copy of it, with the plan's out_offsets) into
+        the cap bytes at d_image (16-byte aligned).  Returns the ZlibReturn: Z_STREAM_ERROR on a plan without
+        zip_enable().  stream: ordered in it like a kernel; the plan's next run, results() and close() wait."""
+        return lib.zsc_hip_deflate_plan_zip(self._h, C.c_void_p(d_output), C.c_void_p(d_image), cap, C.c_void_p(stream))
+
+    def zip_results(self) -> dict:
+        """Waits for the last zip(): {"arch_offsets" (narchives + 1), "arch_lens", "arch_statuses", "entry_offsets"
+        and "data_offsets" (count: where a buffer's local header and its DEFLATE body start), "dir_offsets"
+        (narchives), "total"}.  A failed archive (Z_BUF_ERROR: a buffer that is not Z_OK; Z_MEM_ERROR: longer than
+        4 294 967 295 bytes) has length 0.  BufferError, with .tables, where the image was longer than cap
+        (nothing was written)."""
+        na = getattr(self, "_zip_archives", 0)
+        aoff, alen, ast = (C.c_uint64 * (na + 1))(), (C.c_uint64 * max(na, 1))(), (C.c_int32 * max(na, 1))()
+        eoff, doff = (C.c_uint64 * max(self.count, 1))(), (C.c_uint64 * max(self.count, 1))()
+        diro, total, ms = (C.c_uint64 * max(na, 1))(), C.c_uint64(), C.c_float()
+        rc = lib.zsc_hip_deflate_plan_zip_results(self._h, aoff, alen, ast, eoff, doff, diro, C.byref(total), C.byref(ms))
+        self._zip_ms = ms.value
+        tables = {"arch_offsets": list(aoff), "arch_lens": list(alen)[:na], "arch_statuses": list(ast)[:na],
+                  "entry_offsets": list(eoff)[:self.count], "data_offsets": list(doff)[:self.count],
+                  "dir_offsets": list(diro)[:na], "total": total.value}
+        if rc == Z_BUF_ERROR:
+            err = BufferError(f"the ZIP image takes {total.value} bytes")
+            err.tables = tables
+            raise err
+        if rc != Z_OK:
+            raise RuntimeError(f"zsc_hip_deflate_plan_zip_results failed: {rc}")
+        return tables
+
+    def zip_ms(self) -> float:
+        """After zip_results(): device time of that zip()'s launches, in milliseconds."""
+        if getattr(self, "_zip_ms", None) is None:
+            raise RuntimeError("no zip_results() yet")
+        return self._zip_ms
 
     def close(self) -> None:
         if self._h:

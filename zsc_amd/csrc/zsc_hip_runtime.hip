@@ -39,6 +39,7 @@
 #include "deflate_verify.h"
 #include "pack.h"
 #include "bgzf.h"
+#include "zip.h"
 #include "lz_parse.h"
 #include "lz_parse_seg.h"
 #include "lz_parse_pipe.h"
@@ -847,6 +848,25 @@ __global__ __launch_bounds__(64) void k_bgzf_member_off(BzFiles F, const uint64_
 __global__ __launch_bounds__(64) void k_bgzf_move(BzMove M, uint8_t *image, const uint8_t *out)
 {
     bz_move_tile(M, image, out, blockIdx.x);
+}
+
+/* kernels 4p-4r (zip.h): a gzip plan's streams as ZIP archives, only for a plan with zsc_hip_deflate_plan_zip_enable.
+ * 4p one wavefront per archive: its length and state; the archives' offsets are 4i-4k over those lengths; 4q one
+ * wavefront per archive (and one more): the offsets of the entries, the directory records and the ends; 4r one
+ * wavefront per tile of the image */
+__global__ __launch_bounds__(64) void k_zip_arch_len(ZpArchives A, uint64_t *arch_len, uint32_t *arch_st)
+{
+    zp_arch_len(A, blockIdx.x, arch_len, arch_st);
+}
+
+__global__ __launch_bounds__(64) void k_zip_part_off(ZpArchives A, const uint64_t *arch_off, uint64_t *parts)
+{
+    zp_part_off(A, blockIdx.x, arch_off, parts);
+}
+
+__global__ __launch_bounds__(64) void k_zip_move(ZpMove M, uint8_t *image, const uint8_t *out, const uint8_t *names)
+{
+    zp_move_tile(M, image, out, names, blockIdx.x);
 }
 
 /* one stream of an inflate batch */
@@ -1965,6 +1985,53 @@ void bgzf_release(BgzfState &bs, uint64_t *scratch_bytes)
     bs.on = bs.ran = false;
 }
 
+/* ZIP archives (zip.h): what a gzip deflate plan holds for them */
+struct ZipState {
+    bool on = false, ran = false, has_datetime = false;
+    uint32_t count = 0, narchives = 0, align = 0, flags = 0;
+    std::vector<uint32_t> arch_first; /* narchives + 1 */
+    std::vector<uint64_t> name_off;   /* count + 1 */
+    uint64_t nparts = 0;
+    uint64_t max_total = 0;           /* the most the image takes */
+    uint64_t cap = 0;                 /* image_cap of the last _zip */
+    DevBuf d_first;                   /* arch_first */
+    DevBuf d_fixed;                   /* narchives: ZpLayout.fixed */
+    DevBuf d_arch_off;                /* narchives + 1: the archives' lengths, scanned in place into their offsets */
+    DevBuf d_arch_st;                 /* narchives: ZP_ST_* */
+    DevBuf d_parts;                   /* nparts + 1 offsets */
+    DevBuf d_kinds;                   /* nparts: what each part is */
+    DevBuf d_arch_of;                 /* count */
+    DevBuf d_slots;                   /* count slot offsets */
+    DevBuf d_name_off;                /* count + 1 */
+    DevBuf d_names;                   /* the names */
+    DevBuf d_datetime;                /* count, where the caller gave them */
+    DevBuf d_sums;                    /* the scan's levels above the archives */
+    uint32_t levels = 1;
+    uint64_t level_n[PK_MAX_LEVELS] = {0}, level_at[PK_MAX_LEVELS] = {0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    Enqueued work; /* the _zip calls, for the plan's next run and its destroy */
+    uint64_t scratch = 0;
+};
+
+/* (the caller has waited for the work) */
+void zip_release(ZipState &zs, uint64_t *scratch_bytes)
+{
+    for (DevBuf *b : {&zs.d_first, &zs.d_fixed, &zs.d_arch_off, &zs.d_arch_st, &zs.d_parts, &zs.d_kinds, &zs.d_arch_of,
+                      &zs.d_slots, &zs.d_name_off, &zs.d_names, &zs.d_datetime, &zs.d_sums})
+        b->release();
+    for (hipEvent_t &e : zs.ev) {
+        if (e)
+            (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    work_release(zs.work);
+    if (scratch_bytes)
+        *scratch_bytes -= zs.scratch;
+    zs.scratch = 0;
+    zs.on = zs.ran = false;
+}
+
 } // namespace
 
 struct zsc_hip_deflate_plan {
@@ -2037,6 +2104,8 @@ struct zsc_hip_deflate_plan {
     PackState pack;
     /* BGZF files (bgzf.h), off unless zsc_hip_deflate_plan_bgzf_enable was called */
     BgzfState bgzf;
+    /* ZIP archives (zip.h), off unless zsc_hip_deflate_plan_zip_enable was called */
+    ZipState zip;
 };
 
 /* is the plan one k_parse_seg_narrow is built for?  Plain buffers in the pipeline schedule that would otherwise
@@ -2137,8 +2206,8 @@ static ZlibReturn plan_create(zsc_hip_deflate_plan **plan_out, U32 count, const 
 static hipError_t plan_wait_all(zsc_hip_deflate_plan *pl)
 {
     const hipError_t a = work_wait(pl->ran), b = work_wait(pl->vf_work), c = work_wait(pl->pack.work),
-                     d = work_wait(pl->bgzf.work);
-    return a != hipSuccess ? a : b != hipSuccess ? b : c != hipSuccess ? c : d;
+                     d = work_wait(pl->bgzf.work), e = work_wait(pl->zip.work);
+    return a != hipSuccess ? a : b != hipSuccess ? b : c != hipSuccess ? c : d != hipSuccess ? d : e;
 }
 
 /* gives back what zsc_hip_deflate_plan_index_enable took (the caller has waited for the plan's work) */
@@ -2391,6 +2460,7 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_run(zsc_hip_deflate_plan *pl, const v
     work_order(pl->vf_work, st);
     work_order(pl->pack.work, st);
     work_order(pl->bgzf.work, st);
+    work_order(pl->zip.work, st);
     pl->last_stream = st;
     const uint8_t *in = (const uint8_t *)d_input;
     uint8_t *out = (uint8_t *)d_output;
@@ -2669,6 +2739,7 @@ extern "C" void zsc_hip_deflate_plan_destroy(zsc_hip_deflate_plan *pl)
     verify_release(pl);
     pack_release(pl->pack, &pl->scratch_bytes);
     bgzf_release(pl->bgzf, &pl->scratch_bytes);
+    zip_release(pl->zip, &pl->scratch_bytes);
     for (hipEvent_t e : pl->events)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : pl->idx_events)
@@ -3163,6 +3234,188 @@ extern "C" ZlibReturn zsc_hip_deflate_plan_bgzf_results(zsc_hip_deflate_plan *pl
     if (ms)
         (void)hipEventElapsedTime(ms, bs.ev[0], bs.ev[1]);
     return tot > bs.cap ? Z_BUF_ERROR : Z_OK;
+}
+
+/* ---- ZIP archives from a gzip deflate plan (zip.h) ---------------------------------------------- */
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_zip_enable(zsc_hip_deflate_plan *pl, U32 narchives, const U32 *arch_first,
+                                                      const U8 *names, const uint64_t *name_offsets,
+                                                      const U32 *dos_datetime, U32 flags, U32 align)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZSC_ASSERT(arch_first != Z_NULL);
+    ZSC_ASSERT(name_offsets != Z_NULL);
+    if (pl->wrap != 2 || pl->sectioned || !pack_align_ok(align) || (flags & ~ZSC_HIP_ZIP_UTF8))
+        return Z_STREAM_ERROR;
+    const uint32_t count = pl->count;
+    std::vector<uint32_t> caps(std::max<uint32_t>(count, 1));
+    std::vector<uint64_t> slots(std::max<uint32_t>(count, 1));
+    for (uint32_t i = 0; i < count; i++) {
+        caps[i] = pl->bufs[i].out_cap;
+        slots[i] = pl->bufs[i].out_off;
+    }
+    ZpLayout Z;
+    if (name_offsets[0] > name_offsets[count] || !zp_layout(count, narchives, arch_first, name_offsets, caps.data(), align, Z))
+        return Z_STREAM_ERROR;
+    const uint64_t names_at = name_offsets[0], names_len = name_offsets[count] - names_at;
+    ZSC_ASSERT(names_len == 0 || names != Z_NULL);
+    /* the new partition beside the old one, which stays where anything fails */
+    ZipState nz;
+    nz.count = count;
+    nz.narchives = narchives;
+    nz.align = align;
+    nz.flags = (flags & ZSC_HIP_ZIP_UTF8) ? 0x0800u : 0u;
+    nz.has_datetime = dos_datetime != Z_NULL;
+    nz.arch_first.assign(arch_first, arch_first + narchives + 1u);
+    nz.name_off.resize((size_t)count + 1u);
+    for (uint32_t i = 0; i <= count; i++) /* (the device's names start at 0) */
+        nz.name_off[i] = name_offsets[i] - names_at;
+    nz.nparts = Z.nparts;
+    nz.max_total = Z.max_total;
+    nz.levels = pk_scan_levels(narchives, nz.level_n);
+    uint64_t nsums = 0;
+    for (uint32_t k = 1; k < nz.levels; k++) {
+        nz.level_at[k] = nsums;
+        nsums += nz.level_n[k] + 1u;
+    }
+    auto up = [](DevBuf &b, const void *src, uint64_t bytes) {
+        return b.ensure(bytes) && (bytes == 0 || hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess);
+    };
+    bool ok = up(nz.d_first, arch_first, ((uint64_t)narchives + 1u) * 4u) && up(nz.d_fixed, Z.fixed.data(), Z.fixed.size() * 8u) &&
+              up(nz.d_kinds, Z.kinds.data(), Z.kinds.size() * 4u) && up(nz.d_arch_of, Z.arch_of.data(), Z.arch_of.size() * 4u) &&
+              up(nz.d_slots, slots.data(), slots.size() * 8u) && up(nz.d_name_off, nz.name_off.data(), nz.name_off.size() * 8u) &&
+              up(nz.d_names, names_len ? names + names_at : Z_NULL, names_len) &&
+              (!nz.has_datetime || up(nz.d_datetime, dos_datetime, (uint64_t)count * 4u)) &&
+              nz.d_arch_off.ensure(((uint64_t)narchives + 1u) * 8u) && nz.d_arch_st.ensure(std::max<uint64_t>(narchives, 1) * 4u) &&
+              nz.d_parts.ensure((Z.nparts + 1u) * 8u) && nz.d_sums.ensure(std::max<uint64_t>(nsums, 1) * 8u);
+    ok = ok && hipEventCreate(&nz.ev[0]) == hipSuccess && hipEventCreate(&nz.ev[1]) == hipSuccess;
+    for (const DevBuf *b : {&nz.d_first, &nz.d_fixed, &nz.d_arch_off, &nz.d_arch_st, &nz.d_parts, &nz.d_kinds, &nz.d_arch_of,
+                            &nz.d_slots, &nz.d_name_off, &nz.d_names, &nz.d_datetime, &nz.d_sums})
+        nz.scratch += b->bytes;
+    if (!ok) {
+        (void)hipGetLastError();
+        zip_release(nz, nullptr);
+        return Z_MEM_ERROR;
+    }
+    if (pl->zip.on) { /* what was there before goes, once what was enqueued with it has run */
+        (void)work_wait(pl->zip.work);
+        zip_release(pl->zip, &pl->scratch_bytes);
+    }
+    pl->zip = nz;
+    pl->zip.on = true;
+    pl->scratch_bytes += nz.scratch;
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_zip(zsc_hip_deflate_plan *pl, const void *d_output, void *d_image,
+                                               uint64_t image_cap, void *hip_stream)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZipState &zs = pl->zip;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!zs.on || ((uintptr_t)d_image & 15u) || ((uintptr_t)d_output & 15u))
+        return Z_STREAM_ERROR;
+    /* the grid comes from the capacity; what the image can be at the most bounds it */
+    const uint64_t tiles = (std::min(image_cap, zs.max_total) + PK_TILE - 1u) / PK_TILE;
+    if (tiles > 0x7fffffffull)
+        return Z_MEM_ERROR;
+    if (tiles && (d_image == Z_NULL || (zs.count && d_output == Z_NULL)))
+        return Z_STREAM_ERROR;
+    (void)hipGetLastError();
+    if (zs.ran && zs.stream != st) /* the tables of the one before may still be in use */
+        HIP_TRY(hipStreamSynchronize(zs.stream), return Z_STREAM_ERROR);
+    zs.stream = st;
+    zs.ran = true;
+    zs.cap = image_cap;
+    (void)hipEventRecord(zs.ev[0], st);
+    ZpArchives A;
+    A.rec = (const uint32_t *)pl->d_res.p;
+    A.arch_first = (const uint32_t *)zs.d_first.p;
+    A.name_off = (const uint64_t *)zs.d_name_off.p;
+    A.fixed = (const uint64_t *)zs.d_fixed.p;
+    A.narchives = zs.narchives;
+    A.count = zs.count;
+    A.align = zs.align;
+    uint64_t *const arch_off = (uint64_t *)zs.d_arch_off.p;
+    if (zs.narchives)
+        hipLaunchKernelGGL(k_zip_arch_len, dim3(zs.narchives), dim3(64), 0, st, A, arch_off, (uint32_t *)zs.d_arch_st.p);
+    const PkLens none = {nullptr, 0u, 0u, PK_NO_STATUS};
+    scan_enqueue(zs.levels, zs.level_n, zs.level_at, (uint64_t *)zs.d_sums.p, none, 1u, arch_off, arch_off, st);
+    hipLaunchKernelGGL(k_zip_part_off, dim3(zs.narchives + 1u), dim3(64), 0, st, A, (const uint64_t *)arch_off,
+                       (uint64_t *)zs.d_parts.p);
+    if (tiles) {
+        ZpMove M;
+        M.parts = (const uint64_t *)zs.d_parts.p;
+        M.kinds = (const uint32_t *)zs.d_kinds.p;
+        M.slot = (const uint64_t *)zs.d_slots.p;
+        M.name_off = (const uint64_t *)zs.d_name_off.p;
+        M.arch_first = (const uint32_t *)zs.d_first.p;
+        M.arch_of = (const uint32_t *)zs.d_arch_of.p;
+        M.datetime = zs.has_datetime ? (const uint32_t *)zs.d_datetime.p : nullptr;
+        M.nparts = (uint32_t)zs.nparts;
+        M.flags = zs.flags;
+        M.cap = image_cap;
+        M.names_len = zs.name_off[zs.count];
+        hipLaunchKernelGGL(k_zip_move, dim3((uint32_t)tiles), dim3(64), 0, st, M, (uint8_t *)d_image,
+                           (const uint8_t *)d_output, (const uint8_t *)zs.d_names.p);
+    }
+    (void)hipEventRecord(zs.ev[1], st);
+    work_note(zs.work, st);
+    HIP_TRY(hipGetLastError(), return Z_STREAM_ERROR);
+    return Z_OK;
+}
+
+extern "C" ZlibReturn zsc_hip_deflate_plan_zip_results(zsc_hip_deflate_plan *pl, uint64_t *arch_offsets,
+                                                       uint64_t *arch_lens, I32 *arch_statuses, uint64_t *entry_offsets,
+                                                       uint64_t *data_offsets, uint64_t *dir_offsets, uint64_t *total,
+                                                       float *ms)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(pl != Z_NULL);
+    ZipState &zs = pl->zip;
+    if (ms)
+        *ms = 0.f;
+    if (total)
+        *total = 0;
+    if (!zs.on || !zs.ran)
+        return Z_STREAM_ERROR;
+    HIP_TRY(hipStreamSynchronize(zs.stream), return Z_STREAM_ERROR);
+    std::vector<uint64_t> parts((size_t)zs.nparts + 1u);
+    std::vector<uint32_t> states(std::max<uint32_t>(zs.narchives, 1));
+    HIP_TRY(hipMemcpy(parts.data(), zs.d_parts.p, parts.size() * 8u, hipMemcpyDeviceToHost), return Z_STREAM_ERROR);
+    if (zs.narchives)
+        HIP_TRY(hipMemcpy(states.data(), zs.d_arch_st.p, (size_t)zs.narchives * 4u, hipMemcpyDeviceToHost),
+                return Z_STREAM_ERROR);
+    const uint64_t tot = parts[(size_t)zs.nparts];
+    for (uint32_t a = 0; a < zs.narchives; a++) {
+        const uint32_t first = zs.arch_first[a], end = zs.arch_first[a + 1u];
+        const uint64_t at = parts[2u * (size_t)first + a], end_at = parts[2u * (size_t)end + a];
+        const bool sound = states[a] == ZP_ST_OK;
+        if (arch_offsets)
+            arch_offsets[a] = at;
+        if (arch_lens)
+            arch_lens[a] = sound ? end_at + zp_end_len(end - first) - at : 0u;
+        if (arch_statuses)
+            arch_statuses[a] = sound ? Z_OK : states[a] == ZP_ST_MEM ? Z_MEM_ERROR : Z_BUF_ERROR;
+        if (dir_offsets)
+            dir_offsets[a] = parts[(size_t)a + end + first]; /* (an empty directory lies where the end does) */
+        for (uint32_t i = first; i < end; i++) {
+            const uint64_t e = parts[(size_t)first + a + i];
+            if (entry_offsets)
+                entry_offsets[i] = e;
+            if (data_offsets)
+                data_offsets[i] = sound ? e + ZP_LOCAL + (zs.name_off[i + 1u] - zs.name_off[i]) : e;
+        }
+    }
+    if (arch_offsets)
+        arch_offsets[zs.narchives] = tot;
+    if (total)
+        *total = tot;
+    if (ms)
+        (void)hipEventElapsedTime(ms, zs.ev[0], zs.ev[1]);
+    return tot > zs.cap ? Z_BUF_ERROR : Z_OK;
 }
 
 /* ---- level 0 --------------------------------------------------------------------- */
@@ -5632,6 +5885,94 @@ extern "C" ZlibReturn zsc_hip_bgzf_compress_batch(U32 nfiles, const U8 *const *s
                 rc = Z_STREAM_ERROR;
             if (statuses)
                 statuses[f] = s;
+        }
+    }
+    (void)hipDeviceSynchronize();
+    for (DevBuf *b : {&d_in, &d_out, &d_image})
+        b->release();
+    zsc_hip_deflate_plan_destroy(pl);
+    return rc;
+}
+
+extern "C" ZlibReturn zsc_hip_zip_compress_batch(U32 narchives, const U32 *arch_first, const U8 *const *sources,
+                                                 const U32 *source_lens, const U8 *names, const uint64_t *name_offsets,
+                                                 const U32 *dos_datetime, U32 flags, U8 *const *dests,
+                                                 uint64_t *dest_lens, I32 *statuses, I32 level, I32 mem_level,
+                                                 ZlibStrategy strategy)
+{
+    DeviceScope scope;
+    ZSC_ASSERT(arch_first != Z_NULL && name_offsets != Z_NULL);
+    ZSC_ASSERT(narchives == 0 || (dests != Z_NULL && dest_lens != Z_NULL));
+    if (level == Z_NO_COMPRESSION)
+        return Z_STREAM_ERROR;
+    const U32 count = arch_first[narchives];
+    ZSC_ASSERT(count == 0 || (sources != Z_NULL && source_lens != Z_NULL));
+    if (count == 0) { /* nothing to compress: every archive is an end record alone */
+        static const U8 kEnd[ZP_END] = {0x50, 0x4b, 5, 6};
+        if (flags & ~ZSC_HIP_ZIP_UTF8)
+            return Z_STREAM_ERROR;
+        for (U32 a = 0; a < narchives; a++)
+            if (arch_first[a] != 0u)
+                return Z_STREAM_ERROR;
+        for (U32 a = 0; a < narchives; a++) {
+            const bool room = dest_lens[a] >= ZP_END;
+            if (room)
+                memcpy(dests[a], kEnd, ZP_END);
+            dest_lens[a] = ZP_END;
+            if (statuses)
+                statuses[a] = room ? Z_OK : Z_BUF_ERROR;
+        }
+        return Z_OK;
+    }
+    if (zsc_hip_init(-1) != Z_OK)
+        return Z_STREAM_ERROR;
+    std::vector<U32> caps(std::max<U32>(count, 1));
+    std::vector<uint64_t> in_off(std::max<U32>(count, 1)), out_off(std::max<U32>(count, 1));
+    uint64_t in_bytes = 0, out_bytes = 0;
+    ZlibReturn rc = zsc_hip_deflate_plan_layout(count, source_lens, level, 31, mem_level, in_off.data(), out_off.data(),
+                                                caps.data(), &in_bytes, &out_bytes);
+    if (rc != Z_OK)
+        return rc;
+    zsc_hip_deflate_plan *pl = nullptr;
+    rc = zsc_hip_deflate_plan_create(&pl, count, source_lens, in_off.data(), out_off.data(), caps.data(), level, 31,
+                                     mem_level, strategy);
+    if (rc != Z_OK)
+        return rc;
+    rc = zsc_hip_deflate_plan_zip_enable(pl, narchives, arch_first, names, name_offsets, dos_datetime, flags, 16u);
+    DevBuf d_in, d_out, d_image;
+    const uint64_t icap = rc == Z_OK ? pl->zip.max_total : 0;
+    if (rc == Z_OK && !(d_in.ensure(in_bytes) && d_out.ensure(out_bytes) && d_image.ensure(icap)))
+        rc = Z_MEM_ERROR;
+    if (rc == Z_OK) { /* one upload: the buffers gathered at the plan's offsets */
+        std::vector<U8> stage((size_t)in_bytes, 0);
+        for (U32 i = 0; i < count; i++)
+            if (source_lens[i])
+                memcpy(stage.data() + in_off[i], sources[i], source_lens[i]);
+        if (in_bytes && hipMemcpy(d_in.p, stage.data(), in_bytes, hipMemcpyHostToDevice) != hipSuccess)
+            rc = Z_STREAM_ERROR;
+    }
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_run(pl, d_in.p, d_out.p, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_zip(pl, d_out.p, d_image.p, icap, nullptr);
+    if (rc == Z_OK)
+        rc = zsc_hip_deflate_plan_results(pl, Z_NULL, Z_NULL);
+    if (rc == Z_OK) {
+        std::vector<uint64_t> off((size_t)narchives + 1u), alen(std::max<U32>(narchives, 1));
+        std::vector<I32> ast(std::max<U32>(narchives, 1));
+        rc = zsc_hip_deflate_plan_zip_results(pl, off.data(), alen.data(), ast.data(), Z_NULL, Z_NULL, Z_NULL, Z_NULL,
+                                              Z_NULL);
+        for (U32 a = 0; rc == Z_OK && a < narchives; a++) { /* ... and one copy out per archive */
+            const uint64_t room = dest_lens[a];
+            dest_lens[a] = alen[a];
+            I32 s = ast[a];
+            if (s == Z_OK && alen[a] > room)
+                s = Z_BUF_ERROR;
+            else if (s == Z_OK &&
+                     hipMemcpy(dests[a], (const uint8_t *)d_image.p + off[a], alen[a], hipMemcpyDeviceToHost) != hipSuccess)
+                rc = Z_STREAM_ERROR;
+            if (statuses)
+                statuses[a] = s;
         }
     }
     (void)hipDeviceSynchronize();
